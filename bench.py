@@ -18,7 +18,12 @@ Workloads (BASELINE.json configs):
   --scaling weak             1920x1080 x 128*N spp, every rank renders its 1/N of the tiles at 128*N spp:
                              per-GPU work fixed; N = 8 is config 3 again
 The primary mode's number is `value` over the full `--steps`; the other mode is measured too (a few steps,
-`--other-steps 0` turns it off) and reported under `other_mode`.
+`--other-steps 0` turns it off) and reported under `other_mode`. `ms_per_step` is the wall time of the `--steps` timed steps
+(between device barriers) over their number. BASELINE configs 4 and 5 are measured only on request (`--sub-configs`).
+
+`--dump-outputs DIR` writes what the last timed step computed — the film iile_render leaves in HBM ({X,Y,Z,w} per pixel) or,
+for --workload iispt, the frame's RGB image — as DIR/<name>.npy (float32). The inputs are fixed by the arguments (scene file or
+seeded generator, Halton / Sobol samples, seeded network weights), so two builds compare output for output.
 
 Rank 0 prints one JSON line. `value` is whole-job Mray/s over the rays the timed kernels traced (a ray = one
 Scene::Intersect or Scene::IntersectP call of the reference; MIS rays that provably cannot end on the sampled light are
@@ -45,6 +50,22 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 HBM_PEAK_GBS = 8000.0    # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
 L2_PEAK_GBS = 34500.0    # aggregate L2 bandwidth, same guide ("L2 (per XCD)")
 VALU_PEAK_TLANEOPS = 256 * 4 * 32 * 2.4e9 / 1e12  # CUs x SIMDs x lanes per clock x max clock: 78.6 T lane-ops/s
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_output(directory, name, array):
+    """--dump-outputs: `array` (float32 / float64, channels last) as directory/<name>.npy. Beyond DUMP_LIMIT_BYTES only a fixed,
+    seeded sample of its pixels is written (rows of the flattened image, in pixel order), the same sample for the same shape."""
+    import numpy as np
+    assert array.dtype in (np.float32, np.float64), array.dtype
+    if array.nbytes > DUMP_LIMIT_BYTES:
+        px = array.reshape(-1, array.shape[-1])
+        keep = DUMP_LIMIT_BYTES // px[0].nbytes
+        array = px[np.sort(np.random.default_rng(0).choice(len(px), keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), array)
 
 
 def algorithmic_bytes(rays, nodes, tris):
@@ -315,6 +336,8 @@ def main_iispt(args):
     barrier()
     elapsed = time.perf_counter() - t0
     frame, img, _ = last
+    if args.dump_outputs and rank == 0:
+        dump_output(args.dump_outputs, "image", img.cpu().numpy())
     probes = frame.stats["probes"]
     if dist is not None:   # the slowest rank's time; every rank's probes (a rank's statistics cover its own tasks)
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -462,13 +485,21 @@ def parse_args(argv=None):
                          "alpha masks and specular materials (the whole feature set of SURVEY.md 8 f1); "
                          "iispt: BASELINE config 5, one frame of the IISPT integrator (probe pass, network, gather, direct pass)")
     ap.add_argument("--net-batch", type=int, default=8192, help="--workload iispt: probes per set of network launches (iile_iispt_net_predict's max_batch)")
-    ap.add_argument("--sub-configs", default="4_room,5_iispt",
+    ap.add_argument("--sub-configs", default="none",
                     help="with the default workload on one GPU: BASELINE configs measured after the headline steps and printed as sub-blocks "
                          "`configs` of the same JSON line (4_room: the deep-tree room, 1080p x 64 spp; 5_iispt: one IISPT frame at 1080p); "
-                         "`none` turns them off")
+                         "default `none`: each sub-block is a whole bench line of its own (it begins {\"metric\": ...), and nested in the "
+                         "headline's they keep a reader of the output from finding where the headline line starts")
     ap.add_argument("--sub-steps", type=int, default=0, help="timed steps of each sub-config (default: 2 for the room, 3 for the IISPT frame)")
     ap.add_argument("--sub-cpu-seconds", type=float, default=6.0, help="cpu_baseline budget of each sub-config")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): film.npy, the film of "
+                         "iile_render ({X,Y,Z,w} per pixel), or image.npy for --workload iispt; at most 64 MB (a fixed, seeded sample of "
+                         "the pixels beyond that)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -500,6 +531,7 @@ def sub_configs(args, subs):
         a = argparse.Namespace(**vars(args))
         a.cpu_seconds = args.sub_cpu_seconds if args.cpu_seconds > 0 else 0.0
         a.other_steps = 0
+        a.dump_outputs = None   # (the headline's film only)
         t0 = time.perf_counter()
         if name == "4_room":
             a.workload, a.steps, a.warmup = "boxroom", args.sub_steps or 2, 1
@@ -582,8 +614,9 @@ def main_path(args):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(total_spp, steps, warmup, want_kernels):
-        """Instrumented step, warm-up, `steps` timed steps between barriers; returns the job's numbers (rank 0)."""
+    def measure(total_spp, steps, warmup, want_kernels, keep_film=False):
+        """Instrumented step, warm-up, `steps` timed steps between barriers; returns the job's numbers (rank 0) and, with
+        keep_film, the last timed step's film on the host (rank 0: the merged film)."""
         scene = b.HostScene(path=args.scene, xres=args.xres, yres=args.yres, spp=total_spp, sampler=args.sampler)
         gpu = b.GpuScene(scene)
         h, w = scene.film_shape
@@ -629,6 +662,7 @@ def main_path(args):
                 agg[k] += st[k]
         barrier()
         elapsed = time.perf_counter() - t0
+        last_film = film.cpu().numpy() if keep_film and rank == 0 else None   # (before the one-stream steps below render into it)
         # this rank's share of a step: its render (iile_render on its tiles) and its part of the one film reduction
         ms_render = sum(e[0].elapsed_time(e[1]) for e in rank_times) / max(len(rank_times), 1)
         ms_reduce = sum(e[1].elapsed_time(e[2]) for e in rank_times) / max(len(rank_times), 1)
@@ -673,13 +707,15 @@ def main_path(args):
                "per_rank": per_rank,
                "alone": alone, "n_alone": n_alone,
                "ms_per_step": elapsed * 1e3 / steps, "mray": traced * steps / elapsed / 1e6,
-               "mray_reference": rays * steps / elapsed / 1e6, "total_spp": total_spp}
+               "mray_reference": rays * steps / elapsed / 1e6, "total_spp": total_spp, "film": last_film}
         del gpu, scene, film, film_check
         torch.cuda.empty_cache()
         return res
 
     modes = {"weak": args.spp * world, "strong": args.strong_spp}
-    primary = measure(modes[args.scaling], args.steps, args.warmup, True)
+    primary = measure(modes[args.scaling], args.steps, args.warmup, True, keep_film=bool(args.dump_outputs))
+    if primary["film"] is not None:
+        dump_output(args.dump_outputs, "film", primary["film"])
     other_name = "strong" if args.scaling == "weak" else "weak"
     other = None
     if args.other_steps > 0 and args.workload == "killeroo" and modes[other_name] != modes[args.scaling]:

@@ -113,7 +113,7 @@ def test_iispt_line_has_the_contract_fields():
 
 
 def test_headline_line_carries_configs_4_and_5():
-    """VERDICT r05 "next" 1: the line the driver runs (`python bench.py --gpus 1 ...`, no other flag) measures BASELINE config 4 (the
+    """VERDICT r05 "next" 1: the line of `python bench.py --gpus 1 --sub-configs 4_room,5_iispt ...` measures BASELINE config 4 (the
     deep room) and config 5 (the IISPT frame) after the headline steps and prints them as sub-blocks of the same JSON line — each a
     whole line of its own workload (ms_per_step, roofline, cpu_baseline, the in-run parity check). The headline keys stay config 2's."""
     d, src = _newest("bench")
@@ -139,7 +139,7 @@ def test_headline_line_carries_configs_4_and_5():
     chk = r["agreement_with_the_module"]
     assert chk["max_abs_err_over_max"] < 1e-5 and chk["elements_within_1e-4_rel_plus_1e-6_of_max"] >= 0.999 and chk["mean_rel_err_where_nonzero"] <= 1e-5
     assert sum(frame["stage_ms_per_step"].values()) <= frame["ms_per_step"] * 1.02
-    # the default run still fits the driver's window: the two blocks add well under a minute
+    # a run with both blocks still fits the driver's window: the two blocks add well under a minute
     assert room["wall_seconds_of_this_block"] + frame["wall_seconds_of_this_block"] < 60
 
 
@@ -153,3 +153,24 @@ def test_iispt_frame_has_no_slow_processes():
     ms = sorted(r["ms_per_step"] for r in runs)
     med = 0.5 * (ms[4] + ms[5])
     assert max(abs(m - med) for m in ms) / med < 0.05, ms
+
+
+def test_bench_arguments_and_dumped_outputs(tmp_path):
+    """`--steps` is the number of timed steps (ms_per_step divides by it: at least 1); the default line measures config 2 alone;
+    `--dump-outputs` writes an array whole when it fits in 64 MB, and beyond that the same seeded sample of its pixels, in pixel
+    order, every time."""
+    import numpy as np
+    import bench
+    assert bench.parse_args(["--steps", "7"]).steps == 7 and bench.parse_args([]).sub_configs == "none"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    film = np.arange(6 * 5 * 4, dtype=np.float32).reshape(6, 5, 4)
+    bench.dump_output(str(tmp_path / "small"), "film", film)
+    assert np.array_equal(np.load(tmp_path / "small" / "film.npy"), film)
+    n = bench.DUMP_LIMIT_BYTES // 16 + 1000   # pixels of 4 float32: just over the limit; pixel i holds i in every channel
+    big = np.repeat(np.arange(n, dtype=np.float32)[:, None], 4, axis=1).reshape(1, n, 4)
+    for name in ("a", "b"):
+        bench.dump_output(str(tmp_path / "big"), name, big)
+    a, b = np.load(tmp_path / "big" / "a.npy"), np.load(tmp_path / "big" / "b.npy")
+    assert a.dtype == np.float32 and a.nbytes <= bench.DUMP_LIMIT_BYTES and np.array_equal(a, b)
+    assert (a == a[:, :1]).all() and (np.diff(a[:, 0]) > 0).all() and len(a) == bench.DUMP_LIMIT_BYTES // 16

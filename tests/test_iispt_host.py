@@ -93,7 +93,9 @@ def test_cli_refuses_an_iispt_frame_it_cannot_render(tmp_path):
     assert p.returncode == 1 and "needs the network's weights" in p.stdout
     p = run("--integrator", "iispt", "--gpus", "2", "--iisptNet=x")   # (one process, two devices: none is there)
     assert p.returncode == 1 and "given up on every device" in p.stdout
-    p = run("--integrator", "iispt", "--gpus", "2", "--gpurank", "0/2", "--rendezvous", str(tmp_path / "rv"), "--iisptNet=x")
+    # (no device visible: on a GPU box rank 0 would otherwise set up a communicator with a rank 1 that never comes)
+    p = run("--integrator", "iispt", "--gpus", "2", "--gpurank", "0/2", "--rendezvous", str(tmp_path / "rv"), "--iisptNet=x",
+            env={"HIP_VISIBLE_DEVICES": "-1"})
     assert p.returncode == 1
     p = run("--integrator", "iispt", "--iisptNet=x", "--iispt_hemi_size=16")
     assert p.returncode == 1 and "32 x 32 probes" in p.stdout
