@@ -70,7 +70,8 @@ typedef struct iile_stats {
     /* counters named after the reference's STAT_COUNTERs (scene.cpp:45-47,
      * triangle.cpp:45, path.cpp:45-46, integrator.cpp:48); filled when collect_stats */
     uint64_t camera_rays, closest_rays, shadow_rays;
-    uint64_t nodes_closest, nodes_any, tri_tests, tri_hits, sphere_tests;
+    uint64_t nodes_closest, nodes_any, tri_tests, tri_hits;
+    uint64_t sphere_tests;        /* quadric tests: every sphere, disk and cylinder test of the traversal */
     uint64_t nee_evals, zero_radiance;
     uint64_t path_length[8];
     /* timings in milliseconds; per-kernel sums filled when time_kernels */
@@ -80,7 +81,7 @@ typedef struct iile_stats {
     uint64_t n_paths;             /* camera samples rendered by this call */
     uint64_t workspace_bytes;     /* HBM held by the wavefront queues */
     /* the extend kernel alone (main-path closest-hit rays): inputs of its roofline */
-    uint64_t ext_rays, ext_nodes, ext_tri_tests, ext_sphere_tests;
+    uint64_t ext_rays, ext_nodes, ext_tri_tests, ext_sphere_tests; /* (ext_sphere_tests: sphere, disk and cylinder tests) */
     uint64_t any_tri_tests;       /* triangle tests of the shadow (any-hit) kernel */
     double ms_shadow, ms_mis, ms_resolve; /* the NEE kernels (ms_resolve: k_mis_lit); ms_connect is their sum */
     /* filled by every render that returns stats: the MIS rays (EstimateDirect's BSDF-sampled rays) the call really
@@ -131,6 +132,13 @@ int iile_test_patch_capacity(iile_scene *scene, uint32_t capacity);
  * stats == NULL the traversal of the uninstrumented render kernels (four-wide steps). */
 int iile_trace_closest(iile_scene *scene, int32_t n, const float *o3, const float *d3, const float *tmax,
                        int32_t *prim, float *tb, iile_stats *stats);
+/* The SurfaceInteraction of a closest hit on a sphere or a quadric (prim[i]: the primitive iile_trace_closest found for ray i; every one
+ * must be a sphere or a quadric), as the shading kernels build it with (u, v) and the derivatives for textures and bump maps
+ * (src/shapes/sphere.cpp:104-155, disk.cpp:73-92, cylinder.cpp:105-139, then Transform::operator()(SurfaceInteraction)). out: per ray
+ * IILE_SHAPE_HIT_FLOATS floats, world space: p, n, shading.n, dpdu, dpdv, dndu, dndv, wo (3 each), then u, v, flip
+ * (reverseOrientation ^ transformSwapsHandedness: 0 or 1), 0. */
+#define IILE_SHAPE_HIT_FLOATS 28
+int iile_shape_hit_attributes(iile_scene *scene, int32_t n, const float *o3, const float *d3, const int32_t *prim, float *out);
 /* BVHAccel::IntersectP on n rays. */
 int iile_trace_any(iile_scene *scene, int32_t n, const float *o3, const float *d3, const float *tmax,
                    int32_t *hit, iile_stats *stats);

@@ -76,6 +76,10 @@ const iile_film_desc *iile_host_scene_film(const iile_host_scene *scene);
 int iile_host_scene_get_info(const iile_host_scene *scene, iile_host_scene_info *info);
 /* Film "string filename" of the scene file ("pbrt.exr" when it names none, src/core/api.cpp MakeFilm / film.cpp:262). */
 const char *iile_host_scene_film_filename(const iile_host_scene *scene);
+/* Disks and cylinders of the scene (iile_scene_desc::n_quadrics; iile_host_scene_info::n_triangles leaves them out), or -1. */
+int32_t iile_host_scene_quadric_count(const iile_host_scene *scene);
+/* iile_quadric number `index` of the scene (iile_scene_desc::quadrics[index]). */
+int iile_host_scene_quadric(const iile_host_scene *scene, int32_t index, iile_quadric *out);
 void iile_host_scene_free(iile_host_scene *scene);
 
 /* Film::to_rgb_array (src/core/film.cpp:187-225) on a film of

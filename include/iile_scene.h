@@ -47,7 +47,8 @@ enum {
     IILE_PRIM_HAS_NORMALS = 1u << 1, /* TriangleMesh::n != null */
     IILE_PRIM_HAS_UV = 1u << 2,      /* TriangleMesh::uv != null */
     IILE_PRIM_FLIP = 1u << 3,        /* reverseOrientation ^ transformSwapsHandedness */
-    IILE_PRIM_HAS_ALPHA = 1u << 4    /* TriangleMesh::alphaMask or shadowAlphaMask: see prim_alpha */
+    IILE_PRIM_HAS_ALPHA = 1u << 4,   /* TriangleMesh::alphaMask or shadowAlphaMask: see prim_alpha */
+    IILE_PRIM_QUADRIC = 1u << 5      /* a disk or a cylinder (iile_quadric); neither this nor IILE_PRIM_SPHERE: a triangle */
 };
 /* prim_alpha values: an image texture index (a "float" imagemap: all three channels of its texels hold
  * the float), or */
@@ -61,6 +62,22 @@ typedef struct iile_sphere {
     int32_t reverse_orientation;
     int32_t swaps_handedness;
 } iile_sphere;
+
+/* Disk (src/shapes/disk.h:48-70) or Cylinder (src/shapes/cylinder.h:48-71) + Shape base, with the clamps of their
+ * constructors: disk phi_max = Radians(Clamp(phimax, 0, 360)); cylinder zmin / zmax ordered, phi_max likewise. */
+#define IILE_MAX_QUADRICS 1024 /* the loader refuses scenes with more; the device checks it again */
+#define IILE_QUADRIC_DISK 0
+#define IILE_QUADRIC_CYLINDER 1
+typedef struct iile_quadric {
+    float o2w[16], o2w_inv[16]; /* ObjectToWorld.m / .mInv */
+    int32_t kind;               /* IILE_QUADRIC_* */
+    float radius;
+    float inner_radius, height; /* disk ("innerradius", "height"); 0 for a cylinder */
+    float zmin, zmax;           /* cylinder; 0 for a disk */
+    float phi_max;              /* radians */
+    int32_t reverse_orientation;
+    int32_t swaps_handedness;
+} iile_quadric;
 
 enum { IILE_MAT_MATTE = 0, IILE_MAT_PLASTIC = 1, IILE_MAT_UBER = 2, IILE_MAT_MIRROR = 3, IILE_MAT_GLASS = 4 };
 
@@ -140,6 +157,7 @@ typedef struct iile_texture {
 #define IILE_LIGHT_DISTANT 3
 #define IILE_LIGHT_AREA_TRIANGLE 4 /* DiffuseAreaLight on one triangle (every triangle of an emitting mesh is a light) */
 #define IILE_LIGHT_INFINITE 5      /* InfiniteAreaLight without an environment map (src/lights/infinite.h:51-84) */
+#define IILE_LIGHT_AREA_QUADRIC 6  /* DiffuseAreaLight on a disk or a cylinder: `prim` is its primitive, `sphere` is -1 */
 typedef struct iile_light {
     float lemit[3];  /* area: Lemit (L * scale); point, spot: I * scale; distant: L * scale */
     int32_t two_sided;
@@ -149,7 +167,7 @@ typedef struct iile_light {
     float w2l[9];    /* spot: rows of the upper 3x3 of WorldToLight (for Falloff, spot.cpp:66-76) */
     float cos_total_width, cos_falloff_start; /* spot */
     float world_radius; /* distant: radius of the scene's bounding sphere (Light::Preprocess, distant.cpp:63-65) */
-    int32_t prim;       /* triangle area light: its primitive, in BVH order */
+    int32_t prim;       /* triangle or quadric area light: its primitive, in BVH order */
     /* Light::nSamples (area and infinite lights: "samples" / "nsamples", diffuse.cpp:140-141, infinite.cpp:181-182; 0 means 1).
      * The path integrator never looks at it (UniformSampleOneLight); the IISPT direct pass's UniformSampleAllLights does
      * (integrator.cpp:54-83): iile_render_direct takes n_samples light samples per vertex from every light, at most 64 per
@@ -256,7 +274,7 @@ typedef struct iile_scene_desc {
     const uint32_t *prim_flags;    /* [n_prims] */
     const int32_t *prim_material;  /* [n_prims] index into materials */
     const int32_t *prim_light;     /* [n_prims] index into lights or -1 */
-    const int32_t *prim_shape;     /* [n_prims] sphere index for spheres, mesh id for triangles */
+    const int32_t *prim_shape;     /* [n_prims] sphere index for spheres, quadric index for quadrics, mesh id for triangles */
     const float *tri_p;            /* [n_prims*9] world-space p0,p1,p2 (unused for spheres) */
     const float *tri_n;            /* [n_prims*9] world-space vertex normals (if HAS_NORMALS) */
     const float *tri_uv;           /* [n_prims*6] (if HAS_UV) */
@@ -286,6 +304,9 @@ typedef struct iile_scene_desc {
     iile_integrator integrator;
     iile_probe_setup probe;
     iile_sobol sobol;
+    /* disks and cylinders (appended last: the layout before them is what it was without them) */
+    int32_t n_quadrics;
+    const iile_quadric *quadrics;
 } iile_scene_desc;
 
 /* One task of the IISPT render runner (IisptScheduleMonitorTask, src/integrators/iisptschedulemonitor.cpp:40-79): the

@@ -92,6 +92,18 @@ class SceneDescHead(ctypes.Structure):
                 ("prim_light", c_vp), ("prim_shape", c_vp), ("tri_p", c_vp)]
 
 
+class Quadric(ctypes.Structure):
+    """iile_quadric (include/iile_scene.h): a disk or a cylinder."""
+    _fields_ = [("o2w", c_f32 * 16), ("o2w_inv", c_f32 * 16), ("kind", c_i32), ("radius", c_f32), ("inner_radius", c_f32),
+                ("height", c_f32), ("zmin", c_f32), ("zmax", c_f32), ("phi_max", c_f32), ("reverse_orientation", c_i32),
+                ("swaps_handedness", c_i32)]
+
+
+QUADRIC_DISK, QUADRIC_CYLINDER = 0, 1
+PRIM_SPHERE, PRIM_FLIP, PRIM_QUADRIC = 1, 8, 32
+LIGHT_AREA_QUADRIC = 6
+
+
 class GpuStats(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("camera_rays closest_rays shadow_rays nodes_closest nodes_any tri_tests "
                                      "tri_hits sphere_tests nee_evals zero_radiance").split()] + [
@@ -117,7 +129,7 @@ HOST_SYMBOLS = ["iile_host_load_pbrt", "iile_host_scene_desc", "iile_host_scene_
                 "iile_host_scene_free", "iile_host_film_to_rgb", "iile_host_write_pfm", "iile_host_last_error", "iile_host_read_image",
                 "iile_host_scene_texture", "iile_host_scene_texture_level", "iile_host_scene_filter_table",
                 "iile_host_sobol_matrices", "iile_host_sobol_vdc", "iile_host_write_exr", "iile_host_write_image",
-                "iile_host_scene_film_filename", "iile_host_scene_light"]
+                "iile_host_scene_film_filename", "iile_host_scene_light", "iile_host_scene_quadric_count", "iile_host_scene_quadric"]
 class NetWeights(ctypes.Structure):
     """iile_iispt_net_weights (include/iile_gpu.h)."""
     _fields_ = [("conv_weight", c_vp * 15), ("conv_bias", c_vp * 15), ("bn_weight", c_vp * 5), ("bn_bias", c_vp * 5),
@@ -130,7 +142,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
-               "iile_trace_closest", "iile_trace_any", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
+               "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
                "iile_bsdf_eval", "iile_bsdf_sample", "iile_trig_probe", "iile_texture_eval", "iile_render_probes",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
@@ -164,6 +176,9 @@ def host_lib():
         lib.iile_host_scene_get_info.argtypes = [c_vp, ctypes.POINTER(HostSceneInfo)]
         lib.iile_host_scene_free.argtypes = [c_vp]
         lib.iile_host_scene_free.restype = None
+        lib.iile_host_scene_quadric_count.argtypes = [c_vp]
+        lib.iile_host_scene_quadric_count.restype = c_i32
+        lib.iile_host_scene_quadric.argtypes = [c_vp, c_i32, ctypes.POINTER(Quadric)]
         lib.iile_host_film_to_rgb.argtypes = [ctypes.POINTER(FilmDesc), c_vp, c_vp]
         lib.iile_host_write_pfm.argtypes = [ctypes.c_char_p, c_vp, c_i32, c_i32]
         lib.iile_host_read_image.argtypes = [ctypes.c_char_p, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp]
@@ -447,6 +462,23 @@ class HostScene:
             raise RuntimeError(host_lib().iile_host_last_error().decode())
         return lt
 
+    @property
+    def quadric_count(self):
+        """Disks and cylinders of the scene (not among info["n_triangles"])."""
+        return int(host_lib().iile_host_scene_quadric_count(self._h))
+
+    def quadric(self, index):
+        """iile_quadric number `index` of the scene (a copy)."""
+        q = Quadric()
+        if host_lib().iile_host_scene_quadric(self._h, int(index), ctypes.byref(q)) != 0:
+            raise RuntimeError(host_lib().iile_host_last_error().decode())
+        return q
+
+    def prim_flags(self):
+        """iile_scene_desc::prim_flags, in BVH order (a copy)."""
+        head = ctypes.cast(self.desc, ctypes.POINTER(SceneDescHead)).contents
+        return np.frombuffer(ctypes.string_at(head.prim_flags, head.n_prims * 4), dtype=np.uint32).copy()
+
     def texture(self, index):
         """(iile_texture, [level arrays (h, w, 3), row 0 = bottom scanline]) of image texture `index`."""
         lib = host_lib()
@@ -540,6 +572,18 @@ class GpuScene:
                                                  prim.ctypes.data, tb.ctypes.data,
                                                  ctypes.byref(st) if instrumented else None), "iile_trace_closest")
         return prim, tb, st.as_dict()
+
+    def shape_hit_attributes(self, o, d, prim):
+        """The SurfaceInteraction of each ray's closest hit on a sphere or a quadric (prim: from trace_closest): a dict of world-space
+        (n, 3) arrays p, n, sn, dpdu, dpdv, dndu, dndv, wo and (n,) arrays u, v, flip (iile_shape_hit_attributes)."""
+        o, d, prim = _f32(o).reshape(-1, 3), _f32(d).reshape(-1, 3), _i32(prim)
+        out = np.empty((len(prim), 28), np.float32)
+        f = gpu_lib().iile_shape_hit_attributes
+        f.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]
+        self._check(f(self._s, len(prim), o.ctypes.data, d.ctypes.data, prim.ctypes.data, out.ctypes.data), "iile_shape_hit_attributes")
+        r = {k: out[:, 3 * i:3 * i + 3] for i, k in enumerate(("p", "n", "sn", "dpdu", "dpdv", "dndu", "dndv", "wo"))}
+        r.update(u=out[:, 24], v=out[:, 25], flip=out[:, 26] != 0)
+        return r
 
     def trace_any(self, o, d, tmax, instrumented=True):
         o, d, tmax = _f32(o), _f32(d), _f32(tmax)

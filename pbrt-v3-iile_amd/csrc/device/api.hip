@@ -50,6 +50,7 @@ struct EventPair {
 struct iile_scene {
     DScene ds;
     std::vector<void *> allocs;
+    std::vector<uint8_t> prim_is_shape;  // per primitive (BVH order): a sphere or a quadric (iile_shape_hit_attributes checks it)
     int n_cus = 256;
     int max_depth = 5;
     int spp = 1;
@@ -579,8 +580,11 @@ int iile_device_zero(void *dev, uint64_t bytes, void *stream) {
 
 static_assert(kLightDiffuseArea == IILE_LIGHT_DIFFUSE_AREA && kLightPoint == IILE_LIGHT_POINT &&
                   kLightSpot == IILE_LIGHT_SPOT && kLightDistant == IILE_LIGHT_DISTANT &&
-                  kLightAreaTriangle == IILE_LIGHT_AREA_TRIANGLE && kLightInfinite == IILE_LIGHT_INFINITE,
+                  kLightAreaTriangle == IILE_LIGHT_AREA_TRIANGLE && kLightInfinite == IILE_LIGHT_INFINITE &&
+                  kLightAreaQuadric == IILE_LIGHT_AREA_QUADRIC,
               "light type codes");
+static_assert(kQuadricDisk == IILE_QUADRIC_DISK && kQuadricCylinder == IILE_QUADRIC_CYLINDER && kMaxQuadrics == IILE_MAX_QUADRICS,
+              "quadric kind codes");
 static_assert(kMatMatte == IILE_MAT_MATTE && kMatPlastic == IILE_MAT_PLASTIC && kMatUber == IILE_MAT_UBER &&
                   kMatMirror == IILE_MAT_MIRROR && kMatGlass == IILE_MAT_GLASS,
               "material type codes");
@@ -592,13 +596,29 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
     if (d->n_prims >= (1 << 24)) return fail(IILE_ERR_UNSUPPORTED, "more than 2^24 primitives");
     if (d->n_spheres > kMaxSpheres || d->n_materials > kMaxMaterials || d->n_lights > kMaxLights)
         return fail(IILE_ERR_UNSUPPORTED, "too many spheres / materials / lights");
+    if (d->n_quadrics < 0 || d->n_quadrics > kMaxQuadrics || (d->n_quadrics > 0 && !d->quadrics))
+        return fail(IILE_ERR_UNSUPPORTED, "too many disks and cylinders");
+    for (int i = 0; i < d->n_quadrics; ++i)
+        if (d->quadrics[i].kind != IILE_QUADRIC_DISK && d->quadrics[i].kind != IILE_QUADRIC_CYLINDER)
+            return fail(IILE_ERR_UNSUPPORTED, "unsupported quadric kind");
+    for (int i = 0; i < d->n_prims; ++i) {  // every primitive names a shape that exists
+        const uint32_t f = d->prim_flags[i];
+        if ((f & IILE_PRIM_SPHERE) && (f & IILE_PRIM_QUADRIC)) return fail(IILE_ERR_ARG, "primitive is both a sphere and a quadric");
+        if ((f & IILE_PRIM_SPHERE) && (d->prim_shape[i] < 0 || d->prim_shape[i] >= d->n_spheres))
+            return fail(IILE_ERR_ARG, "sphere primitive without its sphere");
+        if ((f & IILE_PRIM_QUADRIC) && (d->prim_shape[i] < 0 || d->prim_shape[i] >= d->n_quadrics))
+            return fail(IILE_ERR_ARG, "quadric primitive without its quadric");
+    }
     for (int i = 0; i < d->n_lights; ++i) {
         const iile_light &l = d->lights[i];
         if (l.type == IILE_LIGHT_DIFFUSE_AREA) {
             if (l.sphere < 0 || l.sphere >= d->n_spheres) return fail(IILE_ERR_ARG, "area light without a sphere");
         } else if (l.type == IILE_LIGHT_AREA_TRIANGLE) {
-            if (l.prim < 0 || l.prim >= d->n_prims || (d->prim_flags[l.prim] & IILE_PRIM_SPHERE) || d->prim_light[l.prim] != i)
+            if (l.prim < 0 || l.prim >= d->n_prims || (d->prim_flags[l.prim] & (IILE_PRIM_SPHERE | IILE_PRIM_QUADRIC)) || d->prim_light[l.prim] != i)
                 return fail(IILE_ERR_ARG, "triangle area light without its triangle");
+        } else if (l.type == IILE_LIGHT_AREA_QUADRIC) {
+            if (l.prim < 0 || l.prim >= d->n_prims || !(d->prim_flags[l.prim] & IILE_PRIM_QUADRIC) || d->prim_light[l.prim] != i)
+                return fail(IILE_ERR_ARG, "quadric area light without its quadric");
         } else if (l.type != IILE_LIGHT_POINT && l.type != IILE_LIGHT_SPOT && l.type != IILE_LIGHT_DISTANT &&
                    l.type != IILE_LIGHT_INFINITE) {
             return fail(IILE_ERR_UNSUPPORTED, "unsupported light type");
@@ -740,14 +760,16 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
         std::vector<float2> uvs(3 * n);
         for (size_t i = 0; i < n; ++i) {
             const float *p = d->tri_p + 9 * i, *nn = d->tri_n + 9 * i, *uv = d->tri_uv + 6 * i;
-            // flag word: bits 0..3 iile_scene.h, bit 4 last primitive of its leaf, bits 5..7 shading
-            // class (material type, +4 for a sphere), bits 8..11 area light index + 1
+            // flag word: bits 0..3 iile_scene.h (bit 0 set for a sphere AND for a quadric: not a triangle, the shape is
+            // told by prim_shape), bit 4 last primitive of its leaf, bits 5..7 shading class (material type, +4 for a
+            // sphere or quadric), bits 8..11 area light index + 1
             const int mt = d->prim_material[i] >= 0 ? d->materials[d->prim_material[i]].type : 3;
-            const uint32_t cls = uint32_t(mt < 0 ? 3 : (mt > 3 ? 3 : mt)) | ((d->prim_flags[i] & 1u) ? 4u : 0u);
+            const bool quadric = (d->prim_flags[i] & IILE_PRIM_QUADRIC) != 0;
+            const uint32_t cls = uint32_t(mt < 0 ? 3 : (mt > 3 ? 3 : mt)) | (((d->prim_flags[i] & 1u) || quadric) ? 4u : 0u);
             const bool masked = (d->prim_flags[i] & IILE_PRIM_HAS_ALPHA) && d->prim_alpha &&
                                 (d->prim_alpha[2 * i] != IILE_ALPHA_NONE || d->prim_alpha[2 * i + 1] != IILE_ALPHA_NONE);
             if (masked) S.has_alpha = 1;  // bit 12 of the flag word
-            uint32_t w[3] = {(d->prim_flags[i] & 15u) | (masked ? 4096u : 0u) | last_in_leaf[i] | (cls == 7u ? 6u : cls) << 5 | (uint32_t(d->prim_light[i] + 1) << 8),
+            uint32_t w[3] = {(d->prim_flags[i] & 15u) | (quadric ? 1u : 0u) | (masked ? 4096u : 0u) | last_in_leaf[i] | (cls == 7u ? 6u : cls) << 5 | (uint32_t(d->prim_light[i] + 1) << 8),
                              uint32_t(d->prim_material[i]), uint32_t(d->prim_light[i])};
             for (int k = 0; k < 3; ++k) {
                 float wf;
@@ -772,8 +794,17 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
         if (rc) return bail(rc);
         rc = upload(sc, uvs.data(), uvs.size(), &S.tri_uv);
         if (rc) return bail(rc);
-        rc = upload(sc, d->prim_shape, n, &S.prim_shape);
-        if (rc) return bail(rc);
+        {
+            // a quadric primitive's shape is ~(its quadric index) on the device: the sign tells the shape's kind (dpath.h)
+            std::vector<int> shape(d->prim_shape, d->prim_shape + n);
+            sc->prim_is_shape.assign(n, 0);
+            for (size_t i = 0; i < n; ++i) {
+                if (d->prim_flags[i] & IILE_PRIM_QUADRIC) shape[i] = ~shape[i];
+                sc->prim_is_shape[i] = (d->prim_flags[i] & (IILE_PRIM_SPHERE | IILE_PRIM_QUADRIC)) ? 1 : 0;
+            }
+            rc = upload(sc, shape.data(), shape.size(), &S.prim_shape);
+            if (rc) return bail(rc);
+        }
         if (S.has_alpha) {
             std::vector<int2> masks(n);
             for (size_t i = 0; i < n; ++i) {
@@ -813,6 +844,23 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
             sp[i].pad_ = 0.f;
         }
         rc = upload(sc, sp.data(), sp.size(), &S.spheres);
+        if (rc) return bail(rc);
+        std::vector<DQuadric> qs(d->n_quadrics);
+        for (int i = 0; i < d->n_quadrics; ++i) {
+            const iile_quadric &q = d->quadrics[i];
+            std::memcpy(qs[i].o2w.m, q.o2w, 64);
+            std::memcpy(qs[i].o2w_inv.m, q.o2w_inv, 64);
+            qs[i].kind = q.kind;
+            qs[i].radius = q.radius;
+            qs[i].inner_radius = q.inner_radius;
+            qs[i].height = q.height;
+            qs[i].zmin = q.zmin;
+            qs[i].zmax = q.zmax;
+            qs[i].phi_max = q.phi_max;
+            qs[i].reverse_orientation = q.reverse_orientation;
+            qs[i].swaps_handedness = q.swaps_handedness;
+        }
+        rc = upload(sc, qs.data(), qs.size(), &S.quadrics);
         if (rc) return bail(rc);
         std::vector<DMaterial> mats(d->n_materials);
         for (int i = 0; i < d->n_materials; ++i) {
@@ -895,6 +943,7 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
             for (int c = 0; c < 3; ++c) lts[i].lemit[c] = d->lights[i].lemit[c];
             lts[i].two_sided = d->lights[i].two_sided;
             lts[i].sphere = d->lights[i].sphere;
+            lts[i].quadric = d->lights[i].type == IILE_LIGHT_AREA_QUADRIC ? d->prim_shape[d->lights[i].prim] : -1;
             lts[i].type = d->lights[i].type;
             for (int c = 0; c < 3; ++c) lts[i].pos[c] = d->lights[i].pos[c];
             for (int c = 0; c < 9; ++c) lts[i].w2l[c] = d->lights[i].w2l[c];
@@ -1033,6 +1082,8 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
     S.n_nodes = d->n_nodes;
     S.n_prims = d->n_prims;
     S.n_spheres = d->n_spheres;
+    S.n_quadrics = d->n_quadrics;
+    S.rare_prims = (S.has_alpha || d->n_quadrics > 0) ? 1 : 0;
     S.n_materials = d->n_materials;
     S.n_lights = d->n_lights;
     std::memcpy(S.raster_to_camera.m, d->camera.raster_to_camera, 64);
@@ -1174,6 +1225,7 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
             S.extended_features = 1;
     if (d->n_lights > 1 || (d->n_lights == 1 && d->lights[0].type != IILE_LIGHT_DIFFUSE_AREA)) S.extended_features = 1;
     if (S.has_infinite) S.extended_features = 1;
+    if (d->n_quadrics > 0) S.extended_features = 1;  // the plain build leaves quadric hits out (shape_hit_interaction<.., QUAD = false>)
     *out = sc;
     return IILE_OK;
 }
@@ -1806,7 +1858,7 @@ int iile_render_direct(iile_scene *sc, const iile_direct_params *prm, double *fi
     if (rc) return rc;
     DScene S = sc->ds;
     // reflected rays carry differentials in textured scenes (SpecularReflect, directprogressiveintegrator.cpp:165-184), built from the
-    // hit's dpdu / dpdv and shading.dndu / dndv (triangles: triangle_interaction; spheres: sphere_interaction<true>)
+    // hit's dpdu / dpdv and shading.dndu / dndv (triangles: triangle_interaction; spheres, quadrics: shape_hit_interaction<true>)
     const bool reflect_diffs = S.textured_materials && S.has_specular;
     if (S.filter_wide) return fail(IILE_ERR_UNSUPPORTED, "iile_render_direct: the direct pass is defined for the one-pixel box film");
     // ("pixelbounds" belongs to the path integrator: the IISPT runner hands DirectProgressiveIntegrator the film's bounds, iisptrenderrunner.cpp:608-613)
@@ -2624,6 +2676,25 @@ int iile_texture_eval(iile_scene *sc, int32_t tex, int32_t n, const float *uv2, 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return dout.get(rgb3, 3 * size_t(n));
+}
+
+static_assert(kShapeHitFloats == IILE_SHAPE_HIT_FLOATS, "shape hit record");
+int iile_shape_hit_attributes(iile_scene *sc, int32_t n, const float *o3, const float *d3, const int32_t *prim, float *out) {
+    if (!sc || n < 0 || !o3 || !d3 || !prim || !out) return fail(IILE_ERR_ARG, "iile_shape_hit_attributes: bad argument");
+    for (int32_t i = 0; i < n; ++i)  // sphere and quadric primitives only: their flag word has bit 0 (api.hip, the vertex records)
+        if (prim[i] < 0 || prim[i] >= sc->ds.n_prims || !(sc->prim_is_shape[size_t(prim[i])]))
+            return fail(IILE_ERR_ARG, "iile_shape_hit_attributes: a primitive is not a sphere or a quadric");
+    DevBuf<float> dox, ddx, dout;
+    DevBuf<int> dp;
+    int rc;
+    if ((rc = dox.put(o3, 3 * size_t(n))) || (rc = ddx.put(d3, 3 * size_t(n))) || (rc = dp.put(prim, size_t(n))) ||
+        (rc = dout.alloc(size_t(kShapeHitFloats) * size_t(n))))
+        return rc;
+    LaunchCfg cfg{sc->n_cus, nullptr, false};
+    if (n) launch_shape_hit_probe(sc->ds, n, dox.p, ddx.p, dp.p, dout.p, cfg);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return dout.get(out, size_t(kShapeHitFloats) * size_t(n));
 }
 
 int iile_trig_probe(int32_t n, const float *x, float *out3) {

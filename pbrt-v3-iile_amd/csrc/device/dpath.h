@@ -611,6 +611,152 @@ DEV void sphere_interaction(const DSphere &sp, F3 obj_d, F3 ph, Isect *is) {
     }
 }
 
+// ===========================================================================
+// Disk and cylinder (shapes/disk.cpp, shapes/cylinder.cpp)
+// ===========================================================================
+// Disk::Intersect / IntersectP up to the hit decision (disk.cpp:48-71, :99-122: the plane test, no error bounds) and
+// Cylinder::Intersect / IntersectP (cylinder.cpp:48-103, :146-201: the EFloat quadratic, the refined hit, the clipping
+// branch with its second root). Outputs the object-space ray direction and the refined hit point for quadric_interaction.
+DEV bool quadric_test(const DQuadric &q, F3 ro, F3 rd, float tmax, float *t_hit, F3 *obj_d, F3 *phit) {
+    F3 oerr, derr;
+    F3 o = xf_point_err(q.o2w_inv, ro, &oerr);
+    F3 d = xf_vector_err(q.o2w_inv, rd, &derr);
+    float len2 = length_sq(d);
+    if (len2 > 0) {  // transform.h:382-394 (tMax unchanged)
+        float dt = dot(vabs(d), oerr) / len2;
+        o = o + d * dt;
+    }
+    if (q.kind == kQuadricDisk) {
+        if (d.z == 0) return false;  // disk.cpp:58-60
+        const float ts = (q.height - o.z) / d.z;
+        if (ts <= 0 || ts >= tmax) return false;
+        F3 ph = o + d * ts;  // :63-71
+        const float dist2 = ph.x * ph.x + ph.y * ph.y;
+        if (dist2 > q.radius * q.radius || dist2 < q.inner_radius * q.inner_radius) return false;
+        float phi = atan2_f(ph.y, ph.x);
+        if (phi < 0) phi += 2 * kPi;
+        if (phi > q.phi_max) return false;
+        ph.z = q.height;  // :84, refined hit point
+        *t_hit = ts;
+        *obj_d = d;
+        *phit = ph;
+        return true;
+    }
+    EF ox = ef(o.x, oerr.x), oy = ef(o.y, oerr.y);
+    EF dx = ef(d.x, derr.x), dy = ef(d.y, derr.y);
+    EF a = dx * dx + dy * dy;  // cylinder.cpp:60-64
+    EF b = ef(2.f) * (dx * ox + dy * oy);
+    EF c = ox * ox + oy * oy - ef(q.radius) * ef(q.radius);
+    EF t0, t1;
+    if (!ef_quadratic(a, b, c, &t0, &t1)) return false;
+    if (t0.hi > tmax || t1.lo <= 0) return false;  // :71-76
+    EF ts = t0;
+    if (ts.lo <= 0) {
+        ts = t1;
+        if (ts.hi > tmax) return false;
+    }
+    // hit point refined onto the cylinder, and its phi (:79-86)
+    auto refined = [&](float t, float *phi) {
+        F3 p = o + d * t;
+        const float hit_rad = sqrtf(p.x * p.x + p.y * p.y);
+        p.x *= q.radius / hit_rad;
+        p.y *= q.radius / hit_rad;
+        *phi = atan2_f(p.y, p.x);
+        if (*phi < 0) *phi += 2 * kPi;
+        return p;
+    };
+    float phi;
+    F3 ph = refined(ts.v, &phi);
+    if (ph.z < q.zmin || ph.z > q.zmax || phi > q.phi_max) {  // :89-103
+        if (ts.v == t1.v) return false;
+        ts = t1;
+        if (t1.hi > tmax) return false;
+        ph = refined(ts.v, &phi);
+        if (ph.z < q.zmin || ph.z > q.zmax || phi > q.phi_max) return false;
+    }
+    *t_hit = ts.v;
+    *obj_d = d;
+    *phit = ph;
+    return true;
+}
+
+// The SurfaceInteraction of a disk hit (disk.cpp:73-92: zero normal derivatives, zero error bounds) or a cylinder hit
+// (cylinder.cpp:105-139: dn/du from the fundamental forms, pError = gamma(3) |(x, y, 0)|), through the SurfaceInteraction
+// constructor (interaction.cpp:19-42) and Transform::operator()(SurfaceInteraction) (transform.cpp:262-297), as
+// sphere_interaction. (With these dp/du, dp/dv the disk's geometric normal is -z in object space, while Disk::Sample gives
+// +z: disk.cpp:78-80 and :133. Reproduced as it is.)
+template <bool DIFFS = false>
+DEV void quadric_interaction(const DQuadric &q, F3 obj_d, F3 ph, Isect *is) {
+    float phi = atan2_f(ph.y, ph.x);
+    if (phi < 0) phi += 2 * kPi;
+    const float u = phi / q.phi_max;
+    float v;
+    F3 dpdu = F3{-q.phi_max * ph.y, q.phi_max * ph.x, 0};
+    F3 dpdv, perr, dndu = F3{0, 0, 0}, dndv = F3{0, 0, 0};
+    if (q.kind == kQuadricDisk) {
+        const float r_hit = sqrtf(ph.x * ph.x + ph.y * ph.y);
+        const float one_minus_v = ((r_hit - q.inner_radius) / (q.radius - q.inner_radius));
+        v = 1 - one_minus_v;
+        const float dr = q.radius - q.inner_radius, inv_r = 1 / r_hit;  // Vector3f / Float multiplies by the reciprocal
+        dpdv = F3{(ph.x * dr) * inv_r, (ph.y * dr) * inv_r, (0.f * dr) * inv_r};
+        perr = F3{0, 0, 0};
+    } else {
+        v = (ph.z - q.zmin) / (q.zmax - q.zmin);
+        dpdv = F3{0, 0, q.zmax - q.zmin};
+        if (DIFFS) {
+            const F3 d2Pduu = (-q.phi_max * q.phi_max) * F3{ph.x, ph.y, 0};
+            const float E = dot(dpdu, dpdu), F = dot(dpdu, dpdv), G = dot(dpdv, dpdv);
+            const F3 N = normalize(cross(dpdu, dpdv));
+            const float e = dot(N, d2Pduu), f = dot(N, F3{0, 0, 0}), g = dot(N, F3{0, 0, 0});
+            const float inv_egf2 = 1 / (E * G - F * F);
+            dndu = ((f * F - e * G) * inv_egf2) * dpdu + ((e * F - f * E) * inv_egf2) * dpdv;
+            dndv = ((g * F - f * G) * inv_egf2) * dpdu + ((f * F - g * E) * inv_egf2) * dpdv;
+        }
+        perr = kGamma3 * vabs(F3{ph.x, ph.y, 0});
+    }
+    F3 n = normalize(cross(dpdu, dpdv));
+    F3 sn = n;
+    if (q.reverse_orientation ^ q.swaps_handedness) {
+        n = n * -1.f;
+        sn = sn * -1.f;
+    }
+    F3 wo = normalize(-obj_d);
+    is->p = xf_point_err2(q.o2w, ph, perr, &is->perr);
+    is->n = normalize(xf_normal(q.o2w_inv, n));
+    is->wo = normalize(xf_vector(q.o2w, wo));
+    F3 snw = normalize(xf_normal(q.o2w_inv, sn));
+    is->sdpdu = xf_vector(q.o2w, dpdu);
+    is->sn = faceforward(snw, is->n);
+    if (DIFFS) {  // (u, v), dp/dv and dn/du, dn/dv for texture lookups, Material::Bump and the direct pass's differentials
+        is->dpdu = is->sdpdu;
+        is->dpdv = is->sdpdv = xf_vector(q.o2w, dpdv);
+        is->dndu = xf_normal(q.o2w_inv, dndu);
+        is->dndv = xf_normal(q.o2w_inv, dndv);
+        is->u = u;
+        is->v = v;
+        is->flip = q.reverse_orientation ^ q.swaps_handedness;
+    }
+}
+
+// The SurfaceInteraction of a closest hit on a sphere or a quadric, `shape` being the primitive's device prim_shape (>= 0: a
+// sphere, ~index: a quadric): the shape's deterministic root selection is redone on the same ray at tMax = inf for the
+// object-space ray and the refined hit point (every tMax-dependent branch of either test is a rejection). QUAD = false: a build
+// that never sees a quadric (k_shade's plain build: a scene with quadrics runs the extended one)
+template <bool DIFFS = false, bool QUAD = true>
+DEV void shape_hit_interaction(const DScene &S, int shape, F3 ro, F3 rd, Isect *is) {
+    float t;
+    F3 od, ph;
+    if (QUAD && shape < 0) {
+        const DQuadric &q = S.quadrics[~shape];
+        quadric_test(q, ro, rd, IILE_INF, &t, &od, &ph);
+        quadric_interaction<DIFFS>(q, od, ph, is);
+    } else {
+        const DSphere &sp = S.spheres[shape];
+        sphere_test(sp, ro, rd, IILE_INF, &t, &od, &ph);
+        sphere_interaction<DIFFS>(sp, od, ph, is);
+    }
+}
+
 // Triangle::Intersect's interaction (triangle.cpp:277-400) from the stored
 // barycentrics of the closest hit.
 DEV void triangle_interaction(const DScene &S, int prim, uint32_t flags, F3 p0, F3 p1, F3 p2, F3 ray_d, float b0,
@@ -1180,7 +1326,8 @@ DEV bool alpha_rejects(const DScene &S, int prim, uint32_t flags, float b0, floa
 
 // ray_d: the float4 record holding the ray direction — only the (rare) sphere
 // test needs it, so it is re-read there instead of living in registers.
-// ALPHA: some mesh of the scene has an alpha mask (vertex-record flag bit 12 marks its triangles)
+// ALPHA: the rare build — some mesh of the scene has an alpha mask (vertex-record flag bit 12 marks its triangles), or the scene
+// has disks or cylinders (DScene::rare_prims): only this build tests quadrics, so the common build stays as it was without them
 template <bool COUNT, bool ALPHA = false>
 DEV bool trav_leaf(const DScene &S, Trav &t, const StackRef &sr, TraceStats *st, const bool any_hit,
                    const float4 *ray_d) {
@@ -1201,14 +1348,18 @@ DEV bool trav_leaf(const DScene &S, Trav &t, const StackRef &sr, TraceStats *st,
             float th;
             F3 od, ph;
             const float4 d4 = *ray_d;
-            // the lanes that test the same sphere go together, the sphere's fields in SGPRs (uniform_entry): one turn of the
-            // loop when the scene has one sphere, which is the common case
-            const int sphere = S.n_spheres == 1 ? 0 : S.prim_shape[prim];
+            // the lanes that test the same sphere or quadric go together, its fields in SGPRs (uniform_entry): one turn of the
+            // loop when the scene has one sphere and no quadric, which is the common case. prim_shape >= 0 is a sphere, ~index a
+            // quadric (disk, cylinder): the kind is decided per turn, on the wave-uniform index
+            const int sphere = (S.n_spheres == 1 && !(ALPHA && S.n_quadrics > 0)) ? 0 : S.prim_shape[prim];
             bool sphere_hit = false;
             for (bool pending = true; pending;) {
                 const int s_now = __builtin_amdgcn_readfirstlane(sphere);
                 if (sphere == s_now) {
-                    sphere_hit = sphere_test(uniform_entry(S.spheres, s_now), t.rc.o(), F3{d4.x, d4.y, d4.z}, t.tmax, &th, &od, &ph);
+                    if (ALPHA && s_now < 0)
+                        sphere_hit = quadric_test(uniform_entry(S.quadrics, ~s_now), t.rc.o(), F3{d4.x, d4.y, d4.z}, t.tmax, &th, &od, &ph);
+                    else
+                        sphere_hit = sphere_test(uniform_entry(S.spheres, s_now), t.rc.o(), F3{d4.x, d4.y, d4.z}, t.tmax, &th, &od, &ph);
                     pending = false;
                 }
             }
@@ -2035,6 +2186,63 @@ DEV float sphere_pdf(const DSphere &sp, const Isect &ref, F3 wi) {
     float cos_tmax = sqrtf(mx(0.f, 1 - sin_tmax2));
     return 1 / (2 * kPi * (1 - cos_tmax));
 }
+// disk and cylinder emitters: Area, Sample(u) (disk.cpp:125-138, cylinder.cpp:204-221) and the solid-angle Shape::Sample(ref, u) /
+// Shape::Pdf(ref, wi) (core/shape.cpp:56-87)
+DEV float quadric_area(const DQuadric &q) {
+    if (q.kind == kQuadricDisk) return float(double(q.phi_max) * 0.5 * double(q.radius * q.radius - q.inner_radius * q.inner_radius));
+    return (q.zmax - q.zmin) * q.radius * q.phi_max;
+}
+DEV LightSample quadric_sample_area(const DQuadric &q, float u0, float u1, float *pdf) {
+    LightSample it;
+    if (q.kind == kQuadricDisk) {
+        // Disk::Sample draws over the full disk of `radius`, whatever innerradius and phimax say (disk.cpp:130-131), while
+        // Area() and Pdf() count the partial disk only: reproduced as it is, not corrected
+        float px, py;
+        concentric_sample_disk(u0, u1, &px, &py);
+        const F3 pobj = F3{px * q.radius, py * q.radius, q.height};
+        it.n = normalize(xf_normal(q.o2w_inv, F3{0, 0, 1}));
+        if (q.reverse_orientation) it.n = it.n * -1.f;
+        it.p = xf_point_err2(q.o2w, pobj, F3{0, 0, 0}, &it.perr);
+    } else {
+        const float z = (1 - u0) * q.zmin + u0 * q.zmax;  // Lerp, pbrt.h
+        const float phi = u1 * q.phi_max;
+        float s, c;
+        sincos_f(phi, &s, &c);
+        F3 pobj = F3{q.radius * c, q.radius * s, z};
+        it.n = normalize(xf_normal(q.o2w_inv, F3{pobj.x, pobj.y, 0}));
+        if (q.reverse_orientation) it.n = it.n * -1.f;
+        const float hit_rad = sqrtf(pobj.x * pobj.x + pobj.y * pobj.y);
+        pobj.x *= q.radius / hit_rad;
+        pobj.y *= q.radius / hit_rad;
+        const F3 pobj_err = kGamma3 * vabs(F3{pobj.x, pobj.y, 0});
+        it.p = xf_point_err2(q.o2w, pobj, pobj_err, &it.perr);
+    }
+    *pdf = 1 / quadric_area(q);
+    return it;
+}
+DEV LightSample quadric_sample(const DQuadric &q, const Isect &ref, float u0, float u1, float *pdf) {
+    LightSample intr = quadric_sample_area(q, u0, u1, pdf);  // Shape::Sample(ref, u, pdf), shape.cpp:56-70
+    F3 wi = intr.p - ref.p;
+    if (length_sq(wi) == 0)
+        *pdf = 0;
+    else {
+        wi = normalize(wi);
+        *pdf *= length_sq(ref.p - intr.p) / absdot(intr.n, -wi);
+        if (is_inf(*pdf)) *pdf = 0.f;
+    }
+    return intr;
+}
+DEV float quadric_pdf(const DQuadric &q, const Isect &ref, F3 wi) {  // Shape::Pdf(ref, wi), shape.cpp:72-87: the shape alone
+    const F3 ro = offset_ray_origin(ref.p, ref.perr, ref.n, wi);
+    float t;
+    F3 od, ph;
+    if (!quadric_test(q, ro, wi, IILE_INF, &t, &od, &ph)) return 0;
+    Isect li;
+    quadric_interaction(q, od, ph, &li);
+    float pdf = length_sq(ref.p - li.p) / (absdot(li.n, -wi) * quadric_area(q));
+    if (is_inf(pdf)) pdf = 0.f;
+    return pdf;
+}
 // InfiniteAreaLight (lights/infinite.cpp:42-174), operation for operation as the oracle's inf_* functions: Lmap is
 // a host-built pyramid among the textures (one texel without an environment map), the Distribution2D a table
 // in HBM: per row {func[w], cdf[w + 1], funcInt}, then the marginal {func[h], cdf[h + 1], funcInt}.
@@ -2112,7 +2320,7 @@ DEV float inf_pdf_li(const DScene &S, const DLight &lt, F3 w) {  // :139-148 wit
 }
 
 // Triangle emitter (shapes/triangle.cpp:546-579) through the generic Shape::Sample(ref, u) /
-// Shape::Pdf(ref, wi) (core/shape.cpp:56-87), and the sphere / triangle dispatch of an area light
+// Shape::Pdf(ref, wi) (core/shape.cpp:56-87), and the sphere / quadric / triangle dispatch of an area light
 DEV float triangle_area(const DScene &S, int prim) {
     const float4 v0 = S.tri_verts[3 * size_t(prim)], v1 = S.tri_verts[3 * size_t(prim) + 1],
                  v2 = S.tri_verts[3 * size_t(prim) + 2];
@@ -2143,6 +2351,7 @@ DEV LightSample triangle_sample_area(const DScene &S, int prim, float u0, float 
 }
 DEV LightSample shape_sample(const DScene &S, const DLight &lt, const Isect &ref, float u0, float u1, float *pdf) {
     if (lt.type == kLightDiffuseArea) return sphere_sample(S.spheres[lt.sphere], ref, u0, u1, pdf);
+    if (lt.type == kLightAreaQuadric) return quadric_sample(S.quadrics[lt.quadric], ref, u0, u1, pdf);
     LightSample intr = triangle_sample_area(S, lt.prim, u0, u1, pdf);  // Shape::Sample(ref, u, pdf), shape.cpp:56-70
     F3 wi = intr.p - ref.p;
     if (length_sq(wi) == 0)
@@ -2159,6 +2368,7 @@ DEV LightSample shape_sample(const DScene &S, const DLight &lt, const Isect &ref
 DEV float shape_pdf(const DScene &S, const DLight &lt, const Isect &ref, F3 wi, unsigned long long *n_tests,
                     unsigned long long *n_hits) {
     if (lt.type == kLightDiffuseArea) return sphere_pdf(S.spheres[lt.sphere], ref, wi);
+    if (lt.type == kLightAreaQuadric) return quadric_pdf(S.quadrics[lt.quadric], ref, wi);
     // Shape::Pdf(ref, wi), shape.cpp:72-87: intersect the shape alone
     const F3 o = offset_ray_origin(ref.p, ref.perr, ref.n, wi);
     const RayCtx rc = make_ray_ctx(o, wi);

@@ -25,6 +25,14 @@ struct DSphere {
     float center[3];
     float pad_;
 };
+// Disk / Cylinder (iile_quadric, shapes/disk.h:48-70, shapes/cylinder.h:48-71)
+enum { kQuadricDisk = 0, kQuadricCylinder = 1 };  // = IILE_QUADRIC_* (checked in api.hip)
+struct DQuadric {
+    M44 o2w, o2w_inv;
+    int kind;
+    float radius, inner_radius, height, zmin, zmax, phi_max;
+    int reverse_orientation, swaps_handedness;
+};
 enum { kMatMatte = 0, kMatPlastic = 1, kMatUber = 2, kMatMirror = 3, kMatGlass = 4 };  // = IILE_MAT_* (checked in api.hip)
 // (16-byte aligned, and the fields every hit reads first: (type, kd) and (ks, alpha) are one float4 each, see make_bsdf)
 struct alignas(16) DMaterial {
@@ -56,21 +64,22 @@ struct DTexture {
     long long level_offset[kMaxTexLevels];
 };
 enum { kLightDiffuseArea = 0, kLightPoint = 1, kLightSpot = 2, kLightDistant = 3, kLightAreaTriangle = 4,
-       kLightInfinite = 5 };  // = IILE_LIGHT_* (checked in api.hip)
+       kLightInfinite = 5, kLightAreaQuadric = 6 };  // = IILE_LIGHT_* (checked in api.hip)
 struct DLight {
     float lemit[3];  // area: Lemit; point: I
     int two_sided;
-    int sphere;
+    int sphere;      // area light on a sphere: its index; else -1
     int type;        // kLight*
     float pos[3];    // point, spot: pLight; distant: wLight
     float w2l[9];    // spot: upper 3x3 of WorldToLight, row major
     float cos_total_width, cos_falloff_start, world_radius;
-    int prim;        // triangle emitter: its primitive
+    int prim;        // triangle or quadric emitter: its primitive
     // infinite light (no map): LightToWorld 3x3 and the 2 x 2 Distribution2D, see iile_scene.h
     float l2w[9];
     int env_tex;            // infinite: Lmap among the textures
     int dist_w, dist_h;     // infinite: size of the Distribution2D
     long long dist_offset;  // its tables in DScene::env_dist
+    int quadric;            // area light on a disk or a cylinder (kLightAreaQuadric): its index in DScene::quadrics; else -1
 };
 // Per Halton dimension: base, float reciprocal and offset of its digit permutation.
 // The digits are peeled in double arithmetic (exact for any u32 index, see
@@ -84,6 +93,7 @@ struct DHaltonDim {
 };
 constexpr int kMaxHaltonDims = 128;
 constexpr int kMaxSpheres = 8;
+constexpr int kMaxQuadrics = 1024;  // = IILE_MAX_QUADRICS (checked in api.hip)
 constexpr int kMaxMaterials = 64;
 constexpr int kMaxLights = 8;
 constexpr int kLightDistStride = 2 * kMaxLights + 2;  // a light distribution: func[kMaxLights], cdf[kMaxLights + 1], funcInt
@@ -114,12 +124,13 @@ struct DScene {
     const float4 *tri_verts;  // 3 float4 per primitive: (p.xyz, w): w0=flags w1=material w2=light
     const float4 *tri_norms;  // 3 float4 per primitive: (n.xyz, uv.{x,y} spread over w)
     const float2 *tri_uv;     // 3 float2 per primitive
-    const int *prim_shape;    // sphere index for sphere primitives
+    const int *prim_shape;    // sphere index for sphere primitives, ~(quadric index) for quadric primitives
     const int2 *prim_alpha;   // {alphaMask, shadowAlphaMask} texture per primitive (has_alpha scenes)
     const uint16_t *perms;
     const DHaltonDim *hdims;
     const uint32_t *pixel_offsets;  // [128*128] Halton index offset of pixel (x mod 128, y mod 128)
     const DSphere *spheres;
+    const DQuadric *quadrics;  // disks and cylinders
     const DMaterial *materials;
     const DLight *lights;
     const DTexture *textures;  // image textures (k_shade<.., TEX = true>)
@@ -129,6 +140,7 @@ struct DScene {
     int n_textures;
     int textured_materials;    // some material reads an image texture
     int n_nodes, n_prims, n_spheres, n_materials, n_lights, n_hdims;
+    int n_quadrics;
     int n_perms;              // u16 entries of `perms`
     float root_box[6];        // bounds of the root node (min.xyz, max.xyz)
     int root_ref;             // >= 0: wide record; < 0: ~first primitive of a single-leaf tree
@@ -146,7 +158,8 @@ struct DScene {
     int has_glass;            // some material transmits: the paths' etaScale is tracked
     int has_uber_trans;       // some uber material has a SpecularTransmission lobe (opacity < 1 or Kt): a vertex can hold two such lobes (k_direct_tree<.., 2>)
     int has_specular;         // some material has a specular lobe (mirror, glass, uber): emitted light after such a bounce
-    int has_alpha;            // some mesh has an alpha mask: the ALPHA builds of the traversal kernels run
+    int has_alpha;            // some mesh has an alpha mask
+    int rare_prims;           // has_alpha, or some primitive is a disk or a cylinder: the ALPHA builds of the traversal kernels run
     int boxes_nested;         // every child box lies inside its parent's (checked at upload): the four-wide
                               // step's skipping of intermediate nodes is exact only then
     // camera

@@ -124,12 +124,8 @@ __global__ __launch_bounds__(kBlock) void k_mis_lit(DScene S, PassBuffers B, int
                     triangle_interaction(S, prim, f2b(v0.w), F3{v0.x, v0.y, v0.z}, F3{v1.x, v1.y, v1.z},
                                          F3{v2.x, v2.y, v2.z}, md, h4.y, h4.z, h4.w, &lis);
                 } else {
-                    const DSphere &sp = S.spheres[lt.sphere];
-                    float th;
-                    F3 od, ph;
-                    // the closest hit was this sphere: redo its root selection for the hit point
-                    sphere_test(sp, mo, md, IILE_INF, &th, &od, &ph);
-                    sphere_interaction(sp, od, ph, &lis);
+                    // the closest hit was this sphere or quadric: redo its root selection for the hit point
+                    shape_hit_interaction(S, lt.type == kLightAreaQuadric ? ~lt.quadric : lt.sphere, mo, md, &lis);
                 }
                 lit = lt.two_sided || dot(lis.n, -md) > 0;
             }
@@ -619,6 +615,25 @@ __global__ void k_texture_probe(DScene S, int n, int tex, const float *uv, const
     out[3 * i] = c.x;
     out[3 * i + 1] = c.y;
     out[3 * i + 2] = c.z;
+}
+// The SurfaceInteraction of a sphere or quadric hit (shape_hit_interaction<DIFFS = true>) for ray i and the primitive its closest
+// hit found (the caller checked that it is not a triangle): kShapeHitFloats floats per ray, see iile_shape_hit_attributes
+__global__ void k_shape_hit_probe(DScene S, int n, const float *o, const float *d, const int *prim, float *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Isect is;
+    shape_hit_interaction<true>(S, S.prim_shape[prim[i]], F3{o[3 * i], o[3 * i + 1], o[3 * i + 2]}, F3{d[3 * i], d[3 * i + 1], d[3 * i + 2]},
+                                &is);
+    const F3 v[8] = {is.p, is.n, is.sn, is.dpdu, is.dpdv, is.dndu, is.dndv, is.wo};
+    float *r = out + size_t(kShapeHitFloats) * i;
+    for (int k = 0; k < 8; ++k) r[3 * k] = v[k].x, r[3 * k + 1] = v[k].y, r[3 * k + 2] = v[k].z;
+    r[24] = is.u;
+    r[25] = is.v;
+    r[26] = is.flip ? 1.f : 0.f;
+    r[27] = 0.f;
+}
+void launch_shape_hit_probe(const DScene &S, int n, const float *o, const float *d, const int *prim, float *out, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_shape_hit_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, o, d, prim, out);
 }
 void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, float *out, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_texture_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, tex, uv, duv, out);

@@ -102,7 +102,7 @@ DEV uint32_t direct_light_request(const DScene &S, const DLight &lt, const Isect
                 nee_flags |= NEE_HAS_MIS;
             }
         }
-    } else if (lt.type != kLightDiffuseArea && lt.type != kLightAreaTriangle) {
+    } else if (lt.type != kLightDiffuseArea && lt.type != kLightAreaTriangle && lt.type != kLightAreaQuadric) {
         // EstimateDirect for a delta light (integrator.cpp:150-166): light sample only. PointLight (lights/point.cpp:
         // 43-52), SpotLight (spot.cpp:53-76), DistantLight (distant.cpp:50-61).
         const F3 pos = F3{lt.pos[0], lt.pos[1], lt.pos[2]};
@@ -178,6 +178,10 @@ DEV uint32_t direct_light_request(const DScene &S, const DLight &lt, const Isect
                 float t_l;
                 F3 od_l, ph_l;
                 can_reach = sphere_test(S.spheres[lt.sphere], m_o, wi, IILE_INF, &t_l, &od_l, &ph_l);
+            } else if (lt.type == kLightAreaQuadric) {  // (the same holds of Disk / Cylinder::Intersect)
+                float t_l;
+                F3 od_l, ph_l;
+                can_reach = quadric_test(S.quadrics[lt.quadric], m_o, wi, IILE_INF, &t_l, &od_l, &ph_l);
             }
             if (can_reach) {
                 unsigned long long nt = 0, nh = 0;
@@ -258,11 +262,7 @@ __global__ __launch_bounds__(kBlock, IILE_DIRECT_SHADE_WAVES) void k_direct_shad
             const uint32_t flags = f2b(v0.w);
             const int material = int(f2b(v1.w)), light = int(f2b(v2.w));
             if (flags & 1u) {
-                float t;
-                F3 od, ph;
-                const DSphere &sp = S.spheres[S.prim_shape[prim]];
-                sphere_test(sp, ray_o, ray_d, IILE_INF, &t, &od, &ph);
-                sphere_interaction<TEX>(sp, od, ph, &is);
+                shape_hit_interaction<TEX>(S, S.prim_shape[prim], ray_o, ray_d, &is);
             } else {
                 triangle_interaction(S, prim, flags, F3{v0.x, v0.y, v0.z}, F3{v1.x, v1.y, v1.z}, F3{v2.x, v2.y, v2.z}, ray_d, h4.y, h4.z,
                                      h4.w, &is);
@@ -510,11 +510,7 @@ TREE_CALL void tree_interaction(const DScene &S, int prim, F3 ro, F3 rd, float b
     *material = int(f2b(v1.w));
     *light = int(f2b(v2.w));
     if (flags & 1u) {
-        float t;
-        F3 od, ph;
-        const DSphere &sp = S.spheres[S.prim_shape[prim]];
-        sphere_test(sp, ro, rd, IILE_INF, &t, &od, &ph);
-        sphere_interaction<TEX>(sp, od, ph, is);
+        shape_hit_interaction<TEX>(S, S.prim_shape[prim], ro, rd, is);
     } else {
         triangle_interaction(S, prim, flags, F3{v0.x, v0.y, v0.z}, F3{v1.x, v1.y, v1.z}, F3{v2.x, v2.y, v2.z}, rd, b0, b1, b2, is);
     }
@@ -542,11 +538,7 @@ TREE_CALL bool tree_mis_lit(const DScene &S, int li, bool hit, const HitRec &hm,
     if (int(f2b(w2.w)) != li) return false;  // lightIsect.primitive->GetAreaLight() == &light
     Isect lis;
     if (f2b(w0.w) & 1u) {
-        float th;
-        F3 od, ph;
-        const DSphere &sp = S.spheres[lt.sphere];
-        sphere_test(sp, mo, md, IILE_INF, &th, &od, &ph);
-        sphere_interaction(sp, od, ph, &lis);
+        shape_hit_interaction(S, lt.type == kLightAreaQuadric ? ~lt.quadric : lt.sphere, mo, md, &lis);
     } else {
         triangle_interaction(S, hm.prim, f2b(w0.w), F3{w0.x, w0.y, w0.z}, F3{w1.x, w1.y, w1.z}, F3{w2.x, w2.y, w2.z}, md, hm.b0, hm.b1, hm.b2, &lis);
     }

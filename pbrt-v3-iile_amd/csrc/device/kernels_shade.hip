@@ -303,13 +303,9 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                 const uint32_t flags = f2b(v0.w);
                 const int material = int(f2b(v1.w)), light = int(f2b(v2.w));
                 if (flags & 1u) {
-                    // the closest hit was the sphere: redo its (deterministic) root
+                    // the closest hit was a sphere or a quadric: redo its (deterministic) root
                     // selection to recover the object-space ray and refined hit point
-                    float t;
-                    F3 od, ph;
-                    const DSphere &sp = S.spheres[S.prim_shape[prim]];
-                    sphere_test(sp, ray_o, ray_d, IILE_INF, &t, &od, &ph);
-                    sphere_interaction<TEX>(sp, od, ph, &is);   // (TEX: with (u, v), dp/du, dp/dv and dn/du, dn/dv for the texture lookups and Material::Bump)
+                    shape_hit_interaction<TEX, EXT>(S, S.prim_shape[prim], ray_o, ray_d, &is);   // (TEX: with (u, v), dp/du, dp/dv and dn/du, dn/dv for the texture lookups and Material::Bump)
                 } else {
                     triangle_interaction(S, prim, flags, F3{v0.x, v0.y, v0.z}, F3{v1.x, v1.y, v1.z},
                                          F3{v2.x, v2.y, v2.z}, ray_d, h4.y, h4.z, h4.w, &is);
@@ -418,7 +414,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                                         nee_flags |= NEE_HAS_MIS;
                                     }
                                 }
-                            } else if (EXT && lt.type != kLightDiffuseArea && lt.type != kLightAreaTriangle) {
+                            } else if (EXT && lt.type != kLightDiffuseArea && lt.type != kLightAreaTriangle && lt.type != kLightAreaQuadric) {
                                 // EstimateDirect for a delta light (integrator.cpp:150-166): light sample
                                 // only, weight 1. Sample_Li of PointLight (lights/point.cpp:43-52),
                                 // SpotLight (spot.cpp:53-76), DistantLight (distant.cpp:50-61).
@@ -515,6 +511,10 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                                         float t_l;
                                         F3 od_l, ph_l;
                                         can_reach = sphere_test(lsp, mo, md, IILE_INF, &t_l, &od_l, &ph_l);
+                                    } else if (EXT && !COUNT && lt.type == kLightAreaQuadric) {  // (the same holds of Disk / Cylinder::Intersect)
+                                        float t_l;
+                                        F3 od_l, ph_l;
+                                        can_reach = quadric_test(S.quadrics[lt.quadric], mo, md, IILE_INF, &t_l, &od_l, &ph_l);
                                     }
                                     if (can_reach) {
                                         const float lp = EXT ? shape_pdf(S, lt, is, wi, &n_pdf_tests, &n_pdf_hits)

@@ -494,7 +494,7 @@ void launch_extend(const DScene &S, const PassDesc &P, const PassBuffers &B, int
     const bool gen = bounce == 0 && P.gen_fused && !cfg.count_stats;
     if (cfg.count_stats)
         hipLaunchKernelGGL((k_extend<true, true, false>), grid, dim3(kTravBlock), 0, cfg.stream, S, P, B, bounce);
-    else if (S.has_alpha) {
+    else if (S.rare_prims) {
         if (gen)
             hipLaunchKernelGGL((k_extend<false, true, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, P, B, bounce);
         else
@@ -512,7 +512,7 @@ void launch_shadow(const DScene &S, const PassBuffers &B, int bounce, uint32_t m
         hipLaunchKernelGGL((k_shadow<true, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
     else
         {
-        if (S.has_alpha)
+        if (S.rare_prims)
             hipLaunchKernelGGL((k_shadow<false, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
         else
             hipLaunchKernelGGL((k_shadow<false, false>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
@@ -525,11 +525,11 @@ void launch_mis(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_
     else
         {
         if (S.all_lights_infinite) {
-            if (S.has_alpha)
+            if (S.rare_prims)
                 hipLaunchKernelGGL((k_mis<false, true, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
             else
                 hipLaunchKernelGGL((k_mis<false, false, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-        } else if (S.has_alpha)
+        } else if (S.rare_prims)
             hipLaunchKernelGGL((k_mis<false, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
         else
             hipLaunchKernelGGL((k_mis<false, false>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);

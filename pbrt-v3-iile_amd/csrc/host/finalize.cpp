@@ -114,6 +114,8 @@ bool finalize_scene(HostScene *s, std::string *err) {
     d.tri_uv = s->o_tri_uv.data();
     d.n_spheres = int(s->spheres.size());
     d.spheres = s->spheres.data();
+    d.n_quadrics = int(s->quadrics.size());
+    d.quadrics = s->quadrics.data();
     d.n_materials = int(s->materials.size());
     d.materials = s->materials.data();
     // Light::Preprocess of DistantLight (distant.cpp:63-65): Scene::WorldBound().BoundingSphere
@@ -127,8 +129,9 @@ bool finalize_scene(HostScene *s, std::string *err) {
         for (iile_light &lt : s->lights)
             if (lt.type == IILE_LIGHT_DISTANT || lt.type == IILE_LIGHT_INFINITE) lt.world_radius = radius;
     }
-    for (size_t i = 0; i < s->o_light.size(); ++i)  // a triangle emitter's primitive, in BVH order
-        if (s->o_light[i] >= 0 && s->lights[size_t(s->o_light[i])].type == IILE_LIGHT_AREA_TRIANGLE)
+    for (size_t i = 0; i < s->o_light.size(); ++i)  // a triangle or quadric emitter's primitive, in BVH order
+        if (s->o_light[i] >= 0 && (s->lights[size_t(s->o_light[i])].type == IILE_LIGHT_AREA_TRIANGLE ||
+                                   s->lights[size_t(s->o_light[i])].type == IILE_LIGHT_AREA_QUADRIC))
             s->lights[size_t(s->o_light[i])].prim = int(i);
     d.n_lights = int(s->lights.size());
     d.lights = s->lights.data();
@@ -340,6 +343,13 @@ bool finalize_scene(HostScene *s, std::string *err) {
                 const float *tp = &s->o_tri_p[9 * size_t(lt.prim)];
                 const V3 p0(tp[0], tp[1], tp[2]), p1(tp[3], tp[4], tp[5]), p2(tp[6], tp[7], tp[8]);
                 const float area = float(0.5 * length(cross(p1 - p0, p2 - p0)));
+                pw[c] = (lt.two_sided ? 2 : 1) * L * area * kPi;
+                break;
+            }
+            case IILE_LIGHT_AREA_QUADRIC: {  // Disk::Area (disk.cpp:125-127), Cylinder::Area (cylinder.cpp:204)
+                const iile_quadric &q = s->quadrics[size_t(s->o_shape[size_t(lt.prim)])];
+                const float area = q.kind == IILE_QUADRIC_DISK ? float(q.phi_max * 0.5 * (q.radius * q.radius - q.inner_radius * q.inner_radius))
+                                                               : (q.zmax - q.zmin) * q.radius * q.phi_max;
                 pw[c] = (lt.two_sided ? 2 : 1) * L * area * kPi;
                 break;
             }

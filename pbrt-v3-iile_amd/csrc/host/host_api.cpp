@@ -94,7 +94,7 @@ int iile_host_scene_get_info(const iile_host_scene *scene, iile_host_scene_info 
     const iile::HostScene &s = scene->s;
     info->n_prims = int(s.prims.size());
     info->n_spheres = int(s.spheres.size());
-    info->n_triangles = info->n_prims - info->n_spheres;
+    info->n_triangles = info->n_prims - info->n_spheres - int(s.quadrics.size());
     info->n_meshes = s.n_meshes;
     info->n_nodes = int(s.nodes.size());
     info->n_interior_nodes = s.n_interior;
@@ -107,6 +107,23 @@ int iile_host_scene_get_info(const iile_host_scene *scene, iile_host_scene_info 
     info->max_depth = s.max_depth;
     info->probe_hemi_size = s.desc.probe.hemi_size;
     info->integrator = s.integrator_iispt ? IILE_INTEGRATOR_IISPT : IILE_INTEGRATOR_PATH;
+    return 0;
+}
+
+int32_t iile_host_scene_quadric_count(const iile_host_scene *scene) {
+    if (!scene) {
+        g_err = "iile_host_scene_quadric_count: null argument";
+        return -1;
+    }
+    return int32_t(scene->s.quadrics.size());
+}
+
+int iile_host_scene_quadric(const iile_host_scene *scene, int32_t index, iile_quadric *out) {
+    if (!scene || !out || index < 0 || size_t(index) >= scene->s.quadrics.size()) {
+        g_err = "iile_host_scene_quadric: null argument or quadric index out of range";
+        return 1;
+    }
+    *out = scene->s.quadrics[size_t(index)];
     return 0;
 }
 

@@ -15,7 +15,7 @@ struct HostPrim {
     uint32_t flags = 0;
     int32_t material = 0;
     int32_t light = -1;
-    int32_t shape = 0;  // sphere index or mesh id
+    int32_t shape = 0;  // sphere index, quadric index or mesh id
     V3 p[3];
     V3 n[3];
     float uv[6] = {0, 0, 0, 0, 0, 0};
@@ -33,6 +33,7 @@ struct HostScene {
     std::vector<HostPrim> prims;  // creation order
     std::vector<HostTexture> textures;
     std::vector<iile_sphere> spheres;
+    std::vector<iile_quadric> quadrics;  // disks and cylinders
     std::vector<iile_material> materials;
     std::vector<iile_light> lights;
     int n_meshes = 0;

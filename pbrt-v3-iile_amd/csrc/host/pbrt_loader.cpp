@@ -895,6 +895,21 @@ class Loader {
         return default_material_;
     }
 
+    // The DiffuseAreaLight of the current AreaLightSource (api.cpp:808-826 MakeAreaLight, lights/diffuse.cpp:125-146): Lemit,
+    // twosided, nSamples; type IILE_LIGHT_DIFFUSE_AREA and no sphere until the caller sets what its shape needs
+    iile_light diffuse_area_light() const {
+        float L[3] = {1, 1, 1}, sc[3] = {1, 1, 1};
+        gs_.area_light_params.rgb("L", L);
+        gs_.area_light_params.rgb("scale", sc);
+        iile_light lt;
+        std::memset(&lt, 0, sizeof(lt));
+        for (int i = 0; i < 3; ++i) lt.lemit[i] = L[i] * sc[i];
+        lt.two_sided = gs_.area_light_params.one_bool("twosided", false);
+        lt.n_samples = gs_.area_light_params.one_int("samples", gs_.area_light_params.one_int("nsamples", 1));
+        lt.sphere = -1;
+        return lt;
+    }
+
     bool make_shape(const std::string &name, const ParamSet &ps) {
         HostScene &s = *scene_;
         const Xform o2w = ctm_;
@@ -926,15 +941,8 @@ class Loader {
             // Shape::WorldBound = ObjectToWorld(ObjectBound()), shape.cpp:54, sphere.cpp:43-46
             pr.world_bound =
                 o2w.bounds(Bounds3(V3(-radius, -radius, sp.zmin), V3(radius, radius, sp.zmax)));
-            if (gs_.has_area_light) {  // api.cpp:808-826 (MakeAreaLight), lights/diffuse.cpp:125-146
-                float L[3] = {1, 1, 1}, sc[3] = {1, 1, 1};
-                gs_.area_light_params.rgb("L", L);
-                gs_.area_light_params.rgb("scale", sc);
-                iile_light lt;
-                std::memset(&lt, 0, sizeof(lt));
-                for (int i = 0; i < 3; ++i) lt.lemit[i] = L[i] * sc[i];
-                lt.two_sided = gs_.area_light_params.one_bool("twosided", false);
-                lt.n_samples = gs_.area_light_params.one_int("samples", gs_.area_light_params.one_int("nsamples", 1));
+            if (gs_.has_area_light) {
+                iile_light lt = diffuse_area_light();
                 lt.sphere = pr.shape;
                 s.lights.push_back(lt);
                 pr.light = int(s.lights.size()) - 1;
@@ -942,6 +950,51 @@ class Loader {
             s.prims.push_back(pr);
             return true;
         }
+        if (name == "disk" || name == "cylinder") {
+            if (s.quadrics.size() >= size_t(IILE_MAX_QUADRICS))
+                return fail("Shape \"" + name + "\": more than " + std::to_string(IILE_MAX_QUADRICS) +
+                            " disks and cylinders in one scene (the GPU renderer's limit)");
+            iile_quadric q;
+            std::memset(&q, 0, sizeof(q));
+            std::memcpy(q.o2w, o2w.m.m, sizeof(q.o2w));
+            std::memcpy(q.o2w_inv, o2w.inv.m, sizeof(q.o2w_inv));
+            q.reverse_orientation = gs_.reverse_orientation;
+            q.swaps_handedness = o2w.swaps_handedness();
+            Bounds3 ob;
+            if (name == "disk") {  // CreateDiskShape, shapes/disk.cpp:140-150, and the constructor, disk.h:50-57
+                q.kind = IILE_QUADRIC_DISK;
+                q.height = ps.one_float("height", 0.f);
+                q.radius = ps.one_float("radius", 1.f);
+                q.inner_radius = ps.one_float("innerradius", 0.f);
+                q.phi_max = radians(clampT(ps.one_float("phimax", 360.f), 0.f, 360.f));
+                ob = Bounds3(V3(-q.radius, -q.radius, q.height), V3(q.radius, q.radius, q.height));  // disk.cpp:43-46
+            } else {  // CreateCylinderShape, shapes/cylinder.cpp:223-233, and the constructor, cylinder.h:50-57
+                q.kind = IILE_QUADRIC_CYLINDER;
+                q.radius = ps.one_float("radius", 1.f);
+                const float zmin = ps.one_float("zmin", -1.f), zmax = ps.one_float("zmax", 1.f);
+                q.zmin = std::min(zmin, zmax);
+                q.zmax = std::max(zmin, zmax);
+                q.phi_max = radians(clampT(ps.one_float("phimax", 360.f), 0.f, 360.f));
+                ob = Bounds3(V3(-q.radius, -q.radius, q.zmin), V3(q.radius, q.radius, q.zmax));  // cylinder.cpp:43-46
+            }
+            s.quadrics.push_back(q);
+            HostPrim pr;
+            pr.flags = IILE_PRIM_QUADRIC | (flip ? IILE_PRIM_FLIP : 0);
+            pr.material = mat;
+            pr.shape = int(s.quadrics.size()) - 1;
+            pr.world_bound = o2w.bounds(ob);  // Shape::WorldBound, shape.cpp:54
+            if (gs_.has_area_light) {
+                iile_light lt = diffuse_area_light();
+                lt.type = IILE_LIGHT_AREA_QUADRIC;
+                lt.prim = -1;  // set once the primitives are in BVH order (finalize_scene)
+                s.lights.push_back(lt);
+                pr.light = int(s.lights.size()) - 1;
+            }
+            s.prims.push_back(pr);
+            return true;
+        }
+        if (name != "plymesh" && name != "trianglemesh" && name != "loopsubdiv")  // cone, paraboloid, hyperboloid, curve, heightfield, nurbs
+            return fail("Shape \"" + name + "\" is not supported (sphere, disk, cylinder, trianglemesh, plymesh, loopsubdiv)");
         std::vector<int> indices;
         std::vector<V3> P, N;
         std::vector<float> uv;
@@ -980,8 +1033,7 @@ class Loader {
             indices.swap(oi);
             P.swap(oP);
             N.swap(oN);
-        } else
-            return fail("Shape \"" + name + "\" is not supported (sphere, trianglemesh, plymesh, loopsubdiv)");
+        }
         // "alpha" / "shadowalpha": a float texture by name, or a float that masks everything when it is 0
         // (CreateTriangleMeshShape, triangle.cpp:689-710; CreatePLYMesh, plymesh.cpp:259-285)
         int alpha_mask[2] = {IILE_ALPHA_NONE, IILE_ALPHA_NONE};
@@ -1034,15 +1086,7 @@ class Loader {
             // Triangle::WorldBound, shapes/triangle.cpp:180-186
             pr.world_bound = bunion(Bounds3(pr.p[0], pr.p[1]), pr.p[2]);
             if (gs_.has_area_light) {  // pbrtShape: one DiffuseAreaLight per shape, i.e. per triangle (api.cpp:1403-1419)
-                float L[3] = {1, 1, 1}, sc[3] = {1, 1, 1};
-                gs_.area_light_params.rgb("L", L);
-                gs_.area_light_params.rgb("scale", sc);
-                iile_light lt;
-                std::memset(&lt, 0, sizeof(lt));
-                for (int i = 0; i < 3; ++i) lt.lemit[i] = L[i] * sc[i];
-                lt.two_sided = gs_.area_light_params.one_bool("twosided", false);
-                lt.n_samples = gs_.area_light_params.one_int("samples", gs_.area_light_params.one_int("nsamples", 1));
-                lt.sphere = -1;
+                iile_light lt = diffuse_area_light();
                 lt.type = IILE_LIGHT_AREA_TRIANGLE;
                 lt.prim = -1;  // set once the primitives are in BVH order (finalize_scene)
                 s.lights.push_back(lt);
