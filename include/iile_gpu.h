@@ -157,6 +157,10 @@ int iile_li_samples(iile_scene *scene, int32_t n, const int32_t *px, const int32
  * {wi.xyz, f.rgb, pdf}) of material `mat` in the canonical frame ns=ng=+z, ss=+x. */
 int iile_bsdf_eval(iile_scene *scene, int32_t n, int32_t mat, const float *wo3, const float *wi3, float *out4);
 int iile_bsdf_sample(iile_scene *scene, int32_t n, int32_t mat, const float *wo3, const float *u2, float *out7);
+/* The same two with the geometric normal ng3 (a unit vector of the frame; BSDF::ng) in place of +z: the shading normal stays +z,
+ * as where a bump map or a mesh's "normal N" tilts it away from the surface. */
+int iile_bsdf_eval_ng(iile_scene *scene, int32_t n, int32_t mat, const float *ng3, const float *wo3, const float *wi3, float *out4);
+int iile_bsdf_sample_ng(iile_scene *scene, int32_t n, int32_t mat, const float *ng3, const float *wo3, const float *u2, float *out7);
 /* The IISPT probe pass: for each of n probes, what iisptrenderrunner.cpp:316-346 obtains from
  * CreateHemisphericCamera(hemi, hemi, pos, dir) + IISPTdIntegrator::RenderView + get_intensity_film /
  * get_normal_film / get_distance_film (src/integrators/iispt_d.cpp:66-470, src/cameras/hemispheric.cpp) — the three

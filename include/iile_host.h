@@ -80,6 +80,8 @@ const char *iile_host_scene_film_filename(const iile_host_scene *scene);
 int32_t iile_host_scene_quadric_count(const iile_host_scene *scene);
 /* iile_quadric number `index` of the scene (iile_scene_desc::quadrics[index]). */
 int iile_host_scene_quadric(const iile_host_scene *scene, int32_t index, iile_quadric *out);
+/* iile_material number `index` of the scene (iile_scene_desc::materials[index]; iile_host_scene_info::n_materials of them). */
+int iile_host_scene_material(const iile_host_scene *scene, int32_t index, iile_material *out);
 void iile_host_scene_free(iile_host_scene *scene);
 
 /* Film::to_rgb_array (src/core/film.cpp:187-225) on a film of

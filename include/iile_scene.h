@@ -79,11 +79,12 @@ typedef struct iile_quadric {
     int32_t swaps_handedness;
 } iile_quadric;
 
-enum { IILE_MAT_MATTE = 0, IILE_MAT_PLASTIC = 1, IILE_MAT_UBER = 2, IILE_MAT_MIRROR = 3, IILE_MAT_GLASS = 4 };
+enum { IILE_MAT_MATTE = 0, IILE_MAT_PLASTIC = 1, IILE_MAT_UBER = 2, IILE_MAT_MIRROR = 3, IILE_MAT_GLASS = 4, IILE_MAT_METAL = 5,
+       IILE_MAT_SUBSTRATE = 6 };
 
-/* MatteMaterial / PlasticMaterial / UberMaterial / MirrorMaterial / GlassMaterial with constant
+/* MatteMaterial / PlasticMaterial / UberMaterial / MirrorMaterial / GlassMaterial / MetalMaterial / SubstrateMaterial with constant
  * textures (src/materials/matte.cpp:45-62, plastic.cpp:45-70, uber.cpp:45-100, mirror.cpp:44-55,
- * glass.cpp:45-92). Uber: its two SpecularTransmission lobes (the pass-through of opacity < 1 and Kt,
+ * glass.cpp:45-92, metal.cpp:58-79, substrate.cpp:45-79). Uber: its two SpecularTransmission lobes (the pass-through of opacity < 1 and Kt,
  * uber.cpp:53-61, 94-99) are rendered by every entry point (the path and probe passes, the IISPT runner's stages, the direct pass).
  * Glass: smooth (uroughness = vroughness = 0: one FresnelSpecular lobe, as the path integrator gets it) or rough
  * (uroughness or vroughness != 0: MicrofacetReflection + MicrofacetTransmission, glass.cpp:66-90). */
@@ -124,6 +125,12 @@ typedef struct iile_material {
      * alpha along u is ("vroughness" not given: roughv = roughu, uber.cpp:83-84), the value for plastic too; >= 0: a float image texture
      * for "vroughness", mapped like rough_tex. rough_tex is then "uroughness" if that parameter is given, else "roughness" (uber.cpp:79-82) */
     int32_t rough_tex_v;
+    /* metal: FresnelConductor(1, eta, k) (metal.cpp:79-80): the conductor's index of refraction and absorption, per RGB channel
+     * (default: the reference's copper, RGBSpectrum::FromSampled of CopperN / CopperK, metal.cpp:90-127); 0 for every other
+     * material. Metal keeps "roughness" / "uroughness" in roughness / alpha / rough_tex and "vroughness" (or "roughness") in
+     * roughness_v / alpha_v / rough_tex_v (-1: the constant): vRough = vRoughness ? vRoughness : roughness (metal.cpp:68-71).
+     * Substrate (substrate.cpp:45-79): FresnelBlend(Kd, Ks) over "uroughness" / "vroughness" in the same fields as metal */
+    float cond_eta[3], cond_k[3];
 } iile_material;
 
 /* ImageTexture<RGBSpectrum, Spectrum> over a UVMapping2D (src/textures/imagemap.h:78-112,

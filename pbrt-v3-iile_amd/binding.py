@@ -99,6 +99,16 @@ class Quadric(ctypes.Structure):
                 ("swaps_handedness", c_i32)]
 
 
+class Material(ctypes.Structure):
+    """iile_material (include/iile_scene.h)."""
+    _fields_ = [("type", c_i32), ("kd", c_f32 * 3), ("ks", c_f32 * 3), ("sigma", c_f32), ("roughness", c_f32), ("alpha", c_f32),
+                ("remap_roughness", c_i32), ("eta", c_f32), ("kr", c_f32 * 3), ("kt", c_f32 * 3), ("on_a", c_f32), ("on_b", c_f32),
+                ("kd_tex", c_i32), ("ks_tex", c_i32), ("kr_tex", c_i32), ("kt_tex", c_i32), ("bump_tex", c_i32), ("rough_tex", c_i32),
+                ("sigma_tex", c_i32), ("opacity", c_f32 * 3), ("roughness_v", c_f32), ("alpha_v", c_f32), ("opacity_tex", c_i32),
+                ("rough_tex_v", c_i32), ("cond_eta", c_f32 * 3), ("cond_k", c_f32 * 3)]
+
+
+MAT_MATTE, MAT_PLASTIC, MAT_UBER, MAT_MIRROR, MAT_GLASS, MAT_METAL, MAT_SUBSTRATE = range(7)
 QUADRIC_DISK, QUADRIC_CYLINDER = 0, 1
 PRIM_SPHERE, PRIM_FLIP, PRIM_QUADRIC = 1, 8, 32
 LIGHT_AREA_QUADRIC = 6
@@ -129,7 +139,8 @@ HOST_SYMBOLS = ["iile_host_load_pbrt", "iile_host_scene_desc", "iile_host_scene_
                 "iile_host_scene_free", "iile_host_film_to_rgb", "iile_host_write_pfm", "iile_host_last_error", "iile_host_read_image",
                 "iile_host_scene_texture", "iile_host_scene_texture_level", "iile_host_scene_filter_table",
                 "iile_host_sobol_matrices", "iile_host_sobol_vdc", "iile_host_write_exr", "iile_host_write_image",
-                "iile_host_scene_film_filename", "iile_host_scene_light", "iile_host_scene_quadric_count", "iile_host_scene_quadric"]
+                "iile_host_scene_film_filename", "iile_host_scene_light", "iile_host_scene_quadric_count", "iile_host_scene_quadric",
+                "iile_host_scene_material"]
 class NetWeights(ctypes.Structure):
     """iile_iispt_net_weights (include/iile_gpu.h)."""
     _fields_ = [("conv_weight", c_vp * 15), ("conv_bias", c_vp * 15), ("bn_weight", c_vp * 5), ("bn_bias", c_vp * 5),
@@ -143,7 +154,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
-               "iile_bsdf_eval", "iile_bsdf_sample", "iile_trig_probe", "iile_texture_eval", "iile_render_probes",
+               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_trig_probe", "iile_texture_eval", "iile_render_probes",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
                "iile_iispt_film_add", "iile_iispt_film_merge",
@@ -179,6 +190,7 @@ def host_lib():
         lib.iile_host_scene_quadric_count.argtypes = [c_vp]
         lib.iile_host_scene_quadric_count.restype = c_i32
         lib.iile_host_scene_quadric.argtypes = [c_vp, c_i32, ctypes.POINTER(Quadric)]
+        lib.iile_host_scene_material.argtypes = [c_vp, c_i32, ctypes.POINTER(Material)]
         lib.iile_host_film_to_rgb.argtypes = [ctypes.POINTER(FilmDesc), c_vp, c_vp]
         lib.iile_host_write_pfm.argtypes = [ctypes.c_char_p, c_vp, c_i32, c_i32]
         lib.iile_host_read_image.argtypes = [ctypes.c_char_p, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp]
@@ -260,6 +272,8 @@ def gpu_lib():
         lib.iile_texture_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_render_probes.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, ctypes.POINTER(GpuStats), c_vp]
         lib.iile_bsdf_sample.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
+        lib.iile_bsdf_eval_ng.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
+        lib.iile_bsdf_sample_ng.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_trig_probe.argtypes = [c_i32, c_vp, c_vp]
         lib.iile_iispt_hemi_points.argtypes = [c_vp, ctypes.POINTER(IisptTask), c_vp, c_vp, c_vp]
         lib.iile_iispt_gather.argtypes = [c_vp, ctypes.POINTER(IisptTask), c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32]
@@ -473,6 +487,13 @@ class HostScene:
         if host_lib().iile_host_scene_quadric(self._h, int(index), ctypes.byref(q)) != 0:
             raise RuntimeError(host_lib().iile_host_last_error().decode())
         return q
+
+    def material(self, index):
+        """iile_material number `index` of the scene (a copy; info["n_materials"] of them)."""
+        m = Material()
+        if host_lib().iile_host_scene_material(self._h, int(index), ctypes.byref(m)) != 0:
+            raise RuntimeError(host_lib().iile_host_last_error().decode())
+        return m
 
     def prim_flags(self):
         """iile_scene_desc::prim_flags, in BVH order (a copy)."""
@@ -737,6 +758,22 @@ class GpuScene:
         out = np.empty((len(wo), 7), np.float32)
         self._check(gpu_lib().iile_bsdf_sample(self._s, len(wo), mat, wo.ctypes.data, u.ctypes.data, out.ctypes.data),
                     "iile_bsdf_sample")
+        return out
+
+    def bsdf_eval_ng(self, mat, ng, wo, wi):
+        """bsdf_eval with the geometric normal ng (3,) in place of +z (the shading normal stays +z)."""
+        ng, wo, wi = _f32(ng).reshape(3), _f32(wo), _f32(wi)
+        out = np.empty((len(wo), 4), np.float32)
+        self._check(gpu_lib().iile_bsdf_eval_ng(self._s, len(wo), mat, ng.ctypes.data, wo.ctypes.data, wi.ctypes.data, out.ctypes.data),
+                    "iile_bsdf_eval_ng")
+        return out
+
+    def bsdf_sample_ng(self, mat, ng, wo, u):
+        """bsdf_sample with the geometric normal ng (3,) in place of +z (the shading normal stays +z)."""
+        ng, wo, u = _f32(ng).reshape(3), _f32(wo), _f32(u)
+        out = np.empty((len(wo), 7), np.float32)
+        self._check(gpu_lib().iile_bsdf_sample_ng(self._s, len(wo), mat, ng.ctypes.data, wo.ctypes.data, u.ctypes.data, out.ctypes.data),
+                    "iile_bsdf_sample_ng")
         return out
 
     def close(self):

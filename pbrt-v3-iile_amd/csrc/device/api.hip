@@ -586,7 +586,8 @@ static_assert(kLightDiffuseArea == IILE_LIGHT_DIFFUSE_AREA && kLightPoint == IIL
 static_assert(kQuadricDisk == IILE_QUADRIC_DISK && kQuadricCylinder == IILE_QUADRIC_CYLINDER && kMaxQuadrics == IILE_MAX_QUADRICS,
               "quadric kind codes");
 static_assert(kMatMatte == IILE_MAT_MATTE && kMatPlastic == IILE_MAT_PLASTIC && kMatUber == IILE_MAT_UBER &&
-                  kMatMirror == IILE_MAT_MIRROR && kMatGlass == IILE_MAT_GLASS,
+                  kMatMirror == IILE_MAT_MIRROR && kMatGlass == IILE_MAT_GLASS && kMatMetal == IILE_MAT_METAL &&
+                  kMatSubstrate == IILE_MAT_SUBSTRATE,
               "material type codes");
 int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
     if (!d || !out) return fail(IILE_ERR_ARG, "iile_scene_create: null argument");
@@ -625,7 +626,7 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
         }
     }
     for (int i = 0; i < d->n_materials; ++i)
-        if (d->materials[i].type < IILE_MAT_MATTE || d->materials[i].type > IILE_MAT_GLASS)
+        if (d->materials[i].type < IILE_MAT_MATTE || d->materials[i].type > IILE_MAT_SUBSTRATE)
             return fail(IILE_ERR_UNSUPPORTED, "unsupported material type");
     if (d->halton.n_dims > kMaxHaltonDims) return fail(IILE_ERR_UNSUPPORTED, "too many Halton dimensions");
     const int need_dims = 5 + 8 * d->integrator.max_depth + 1;
@@ -871,7 +872,12 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
                 mats[i].ks[c] = m.ks[c];
             }
             mats[i].alpha = m.alpha;
-            mats[i].alpha_y = m.type == IILE_MAT_GLASS ? m.alpha_v : (m.type == IILE_MAT_UBER && m.rough_tex_v != -2) ? m.alpha_v : m.alpha;
+            const bool uv_rough = m.type == IILE_MAT_METAL || m.type == IILE_MAT_SUBSTRATE;  // "uroughness" and "vroughness" of their own
+            mats[i].alpha_y = (m.type == IILE_MAT_GLASS || uv_rough) ? m.alpha_v : (m.type == IILE_MAT_UBER && m.rough_tex_v != -2) ? m.alpha_v : m.alpha;
+            for (int c = 0; c < 3; ++c) {
+                mats[i].cond_eta[c] = m.type == IILE_MAT_METAL ? m.cond_eta[c] : 0.f;
+                mats[i].cond_k[c] = m.type == IILE_MAT_METAL ? m.cond_k[c] : 0.f;
+            }
             for (int c = 0; c < 3; ++c) mats[i].kr[c] = m.kr[c];
             for (int c = 0; c < 3; ++c) mats[i].kt[c] = m.kt[c];
             const bool oren_nayar = m.type == IILE_MAT_MATTE && m.sigma != 0;
@@ -894,7 +900,7 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
             mats[i].kr_tex = d->n_textures > 0 ? m.kr_tex : -1;
             mats[i].kt_tex = d->n_textures > 0 ? m.kt_tex : -1;
             mats[i].opacity_tex = (d->n_textures > 0 && m.type == IILE_MAT_UBER) ? m.opacity_tex : -1;
-            mats[i].rough_tex_v = m.type == IILE_MAT_UBER ? ((m.rough_tex_v >= 0 && d->n_textures == 0) ? -1 : m.rough_tex_v) : -2;
+            mats[i].rough_tex_v = (m.type == IILE_MAT_UBER || uv_rough) ? ((m.rough_tex_v >= 0 && d->n_textures == 0) ? -1 : m.rough_tex_v) : -2;
             mats[i].bump_tex = d->n_textures > 0 ? m.bump_tex : -1;
             mats[i].rough_tex = d->n_textures > 0 ? m.rough_tex : -1;
             mats[i].sigma_tex = d->n_textures > 0 ? m.sigma_tex : -1;
@@ -1218,7 +1224,9 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
     S.extended_features = 0;
     S.has_specular = 0;
     for (int i = 0; i < d->n_materials; ++i)
-        if (d->materials[i].type != IILE_MAT_MATTE && d->materials[i].type != IILE_MAT_PLASTIC) S.has_specular = 1;
+        if (d->materials[i].type != IILE_MAT_MATTE && d->materials[i].type != IILE_MAT_PLASTIC && d->materials[i].type != IILE_MAT_METAL &&
+            d->materials[i].type != IILE_MAT_SUBSTRATE)
+            S.has_specular = 1;   // (metal and substrate: one glossy reflection lobe each, metal.cpp:79, substrate.cpp:62)
     for (int i = 0; i < d->n_materials; ++i)
         if ((d->materials[i].type != IILE_MAT_MATTE && d->materials[i].type != IILE_MAT_PLASTIC) ||
             (d->materials[i].type == IILE_MAT_MATTE && d->materials[i].sigma != 0))
@@ -2643,9 +2651,11 @@ int iile_li_samples(iile_scene *sc, int32_t n, const int32_t *px, const int32_t 
 }
 
 static int bsdf_probe(iile_scene *sc, int32_t n, int32_t mat, const float *wo3, const float *in, size_t in_stride,
-                      int sample, float *out, size_t out_stride) {
+                      int sample, float *out, size_t out_stride, const float *ng3 = nullptr) {
     if (!sc || n < 0 || !wo3 || !in || !out || mat < 0 || mat >= sc->ds.n_materials)
         return fail(IILE_ERR_ARG, "iile_bsdf: bad argument");
+    const float up[3] = {0.f, 0.f, 1.f};
+    if (!ng3) ng3 = up;
     int rc = ensure_device();
     if (rc) return rc;
     DevBuf<float> dwo, din, dout;
@@ -2653,7 +2663,7 @@ static int bsdf_probe(iile_scene *sc, int32_t n, int32_t mat, const float *wo3, 
         (rc = dout.alloc(out_stride * size_t(n))))
         return rc;
     LaunchCfg cfg{sc->n_cus, nullptr, false};
-    if (n) launch_bsdf_probe(sc->ds, n, mat, dwo.p, din.p, sample, dout.p, cfg);
+    if (n) launch_bsdf_probe(sc->ds, n, mat, dwo.p, din.p, sample, dout.p, ng3, cfg);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return dout.get(out, out_stride * size_t(n));
@@ -2663,6 +2673,14 @@ int iile_bsdf_eval(iile_scene *sc, int32_t n, int32_t mat, const float *wo3, con
 }
 int iile_bsdf_sample(iile_scene *sc, int32_t n, int32_t mat, const float *wo3, const float *u2, float *out7) {
     return bsdf_probe(sc, n, mat, wo3, u2, 2, 1, out7, 7);
+}
+int iile_bsdf_eval_ng(iile_scene *sc, int32_t n, int32_t mat, const float *ng3, const float *wo3, const float *wi3, float *out4) {
+    if (!ng3) return fail(IILE_ERR_ARG, "iile_bsdf_eval_ng: null normal");
+    return bsdf_probe(sc, n, mat, wo3, wi3, 3, 0, out4, 4, ng3);
+}
+int iile_bsdf_sample_ng(iile_scene *sc, int32_t n, int32_t mat, const float *ng3, const float *wo3, const float *u2, float *out7) {
+    if (!ng3) return fail(IILE_ERR_ARG, "iile_bsdf_sample_ng: null normal");
+    return bsdf_probe(sc, n, mat, wo3, u2, 2, 1, out7, 7, ng3);
 }
 
 int iile_texture_eval(iile_scene *sc, int32_t tex, int32_t n, const float *uv2, const float *duv4, float *rgb3) {

@@ -1444,11 +1444,17 @@ struct Bsdf {
     int n_lobes;  // nBxDFs; BxDF order: [pass-through], Lambertian, microfacet, specular reflection, [uber's Kt lobe]
     float on_a, on_b;  // Oren-Nayar constants of the diffuse lobe (oren_nayar set)
     bool oren_nayar;
-    int mtype;    // kMat*: selects the Fresnel terms (plastic 1.5/1; uber 1/eta; mirror none) and, for
-                  // glass, makes the specular lobe a FresnelSpecular(kr, kt, 1, eta)
+    int mtype;    // kMat*: selects the Fresnel terms (plastic 1.5/1; uber 1/eta; mirror none; metal FresnelConductor(1, kr, kt))
+                  // and, for glass, makes the specular lobe a FresnelSpecular(kr, kt, 1, eta)
     bool has_lambert, has_micro, has_spec;
+    // metal (metal.cpp:58-79): the microfacet lobe is MicrofacetReflection(1, distrib, FresnelConductor(1, eta, k)), its eta and k
+    // held in kr and kt (a metal has no specular lobe that would read them: has_spec is false)
+    // substrate (substrate.cpp:45-66): FresnelBlend(Rd = kd, Rs = ks, distrib) — glossy reflection, the only lobe of its BSDF
+    bool has_blend;
 };
-DEV int n_nonspec(const Bsdf &b) { return (b.has_lambert ? 1 : 0) + (b.has_micro ? 1 : 0) + (b.has_mtrans ? 1 : 0); }
+DEV int n_nonspec(const Bsdf &b) {
+    return (b.has_lambert ? 1 : 0) + (b.has_micro ? 1 : 0) + (b.has_mtrans ? 1 : 0) + (b.has_blend ? 1 : 0);
+}
 DEV F3 to_local(const Bsdf &b, F3 v) { return F3{dot(v, b.ss), dot(v, b.ts), dot(v, b.ns)}; }
 DEV F3 to_world(const Bsdf &b, F3 v) {
     return F3{b.ss.x * v.x + b.ts.x * v.y + b.ns.x * v.z, b.ss.y * v.x + b.ts.y * v.y + b.ns.y * v.z,
@@ -1685,8 +1691,8 @@ DEV DMaterial textured_material(const DScene &S, const DMaterial &m, const Isect
     return r;
 }
 
-// Matte / Plastic / Uber / Mirror ComputeScatteringFunctions (matte.cpp:45-62, plastic.cpp:45-70,
-// uber.cpp:45-100 with opacity 1 and Kt 0, mirror.cpp:44-55)
+// Matte / Plastic / Uber / Mirror / Glass / Metal / Substrate ComputeScatteringFunctions (matte.cpp:45-62, plastic.cpp:45-70,
+// uber.cpp:45-100, mirror.cpp:44-55, glass.cpp:45-92, metal.cpp:58-79, substrate.cpp:45-66)
 // EXT = false: the scene has matte and plastic only (checked at upload); the specular lobes then fold away
 template <bool EXT = true>
 DEV Bsdf make_bsdf(const DMaterial &m, const Isect &is) {
@@ -1716,12 +1722,12 @@ DEV Bsdf make_bsdf(const DMaterial &m, const Isect &is) {
     }
     b.kd = F3{clampf(m_kd.y, 0, IILE_INF), clampf(m_kd.z, 0, IILE_INF), clampf(m_kd.w, 0, IILE_INF)};
     if (uber) b.kd = op * b.kd;
-    b.has_lambert = !is_black(b.kd);
+    b.has_lambert = !is_black(b.kd) && !(EXT && m_type == kMatSubstrate);   // (substrate's Kd is FresnelBlend's Rd)
     if (b.has_lambert) ++b.n_lobes;
     b.ks = F3{0, 0, 0};
     b.has_micro = false;
     b.alpha = m_ks.w;
-    b.alpha_y = (EXT && (m_type == kMatUber || m_type == kMatGlass)) ? m.alpha_y : b.alpha;   // (uber with a roughness image: textured_material sets both)
+    b.alpha_y = (EXT && (m_type == kMatUber || m_type == kMatGlass || m_type == kMatMetal || m_type == kMatSubstrate)) ? m.alpha_y : b.alpha;   // (uber with a roughness image: textured_material sets both)
     b.oren_nayar = EXT && m_type == kMatMatte && m.on_b != 0.f;  // matte.cpp:56-61 (B == 0 iff sigma == 0)
     b.on_a = m.on_a;
     b.on_b = m.on_b;
@@ -1762,6 +1768,19 @@ DEV Bsdf make_bsdf(const DMaterial &m, const Isect &is) {
         b.has_spec = !(is_black(b.kr) && is_black(b.kt));
         if (b.has_spec) ++b.n_lobes;
     }
+    if (EXT && m_type == kMatMetal) {  // metal.cpp:66-78: MicrofacetReflection(1., TR(uRough, vRough), FresnelConductor(1., eta, k))
+        b.ks = F3{1.f, 1.f, 1.f};
+        b.has_micro = true;
+        ++b.n_lobes;
+        b.kr = F3{m.cond_eta[0], m.cond_eta[1], m.cond_eta[2]};   // eta
+        b.kt = F3{m.cond_k[0], m.cond_k[1], m.cond_k[2]};         // k
+    }
+    b.has_blend = false;
+    if (EXT && m_type == kMatSubstrate) {  // substrate.cpp:53-65: d = Kd.Clamp(), s = Ks.Clamp(); no lobe when both are black
+        b.ks = F3{clampf(m_ks.x, 0, IILE_INF), clampf(m_ks.y, 0, IILE_INF), clampf(m_ks.z, 0, IILE_INF)};
+        b.has_blend = !(is_black(b.kd) && is_black(b.ks));
+        if (b.has_blend) ++b.n_lobes;
+    }
     return b;
 }
 // reflection.h:56-84
@@ -1798,6 +1817,27 @@ DEV float fr_dielectric(float cos_i, float eta_i, float eta_t) {
     float r_parl = ((eta_t * cos_i) - (eta_i * cos_t)) / ((eta_t * cos_i) + (eta_i * cos_t));
     float r_perp = ((eta_i * cos_i) - (eta_t * cos_t)) / ((eta_i * cos_i) + (eta_t * cos_t));
     return (r_parl * r_parl + r_perp * r_perp) / 2;
+}
+// FrConductor, reflection.cpp:71-94, with etai = 1 (FresnelConductor(1., eta, k), metal.cpp:76-77): per channel, the Spectrum
+// operations in the reference's order
+DEV float fr_conductor_1(float cos_i, float eta, float k) {
+    const float cos2 = cos_i * cos_i;
+    const float sin2 = float(1. - double(cos2));
+    const float eta2 = eta * eta, etak2 = k * k;
+    const float t0 = eta2 - etak2 - sin2;
+    const float a2plusb2 = sqrtf(t0 * t0 + 4 * eta2 * etak2);
+    const float t1 = a2plusb2 + cos2;
+    const float a = sqrtf(0.5f * (a2plusb2 + t0));
+    const float t2 = (2.f * cos_i) * a;
+    const float rs = (t1 - t2) / (t1 + t2);
+    const float t3 = cos2 * a2plusb2 + sin2 * sin2;
+    const float t4 = t2 * sin2;
+    const float rp = rs * (t3 - t4) / (t3 + t4);
+    return 0.5f * (rp + rs);
+}
+DEV F3 fr_conductor(float cos_i, F3 eta, F3 k) {
+    cos_i = clampf(cos_i, -1, 1);
+    return F3{fr_conductor_1(cos_i, eta.x, k.x), fr_conductor_1(cos_i, eta.y, k.y), fr_conductor_1(cos_i, eta.z, k.z)};
 }
 // TrowbridgeReitzDistribution::D / Lambda, microfacet.cpp:155-163, 176-184
 // (ax, ay: alphax, alphay. Where the scene has no anisotropic material — the plain build always — the two are one value and the
@@ -1871,21 +1911,46 @@ DEV F3 tr_sample_wh(F3 wo, float u0, float u1, float ax, float ay) {
     if (flip) wh = -wh;
     return wh;
 }
-// MicrofacetReflection::f, reflection.cpp:226-236, with FresnelDielectric(1.5, 1) (plastic) or (1, e) (uber)
+// MicrofacetReflection::f, reflection.cpp:226-236, with FresnelDielectric(1.5, 1) (plastic) or (1, e) (uber, glass), or
+// FresnelConductor(1, eta, k) (metal: its Evaluate takes |cos|, reflection.cpp:118-120)
 DEV F3 micro_f(const Bsdf &b, F3 wo, F3 wi) {
     float cos_o = fabsf(wo.z), cos_i = fabsf(wi.z);
     F3 wh = wi + wo;
     if (cos_i == 0 || cos_o == 0) return F3{0, 0, 0};
     if (wh.x == 0 && wh.y == 0 && wh.z == 0) return F3{0, 0, 0};
     wh = normalize(wh);
-    float Fr = (b.mtype == kMatUber || b.mtype == kMatGlass) ? fr_dielectric(dot(wi, wh), 1.f, b.eta) : fr_dielectric(dot(wi, wh), 1.5f, 1.f);
-    F3 F = F3{Fr, Fr, Fr};
+    F3 F;
+    if (b.mtype == kMatMetal) {
+        F = fr_conductor(fabsf(dot(wi, wh)), b.kr, b.kt);
+    } else {
+        float Fr = (b.mtype == kMatUber || b.mtype == kMatGlass) ? fr_dielectric(dot(wi, wh), 1.f, b.eta) : fr_dielectric(dot(wi, wh), 1.5f, 1.f);
+        F = F3{Fr, Fr, Fr};
+    }
     return sdiv(b.ks * tr_d(wh, b.alpha, b.alpha_y) * tr_g(wo, wi, b.alpha, b.alpha_y) * F, 4 * cos_i * cos_o);
 }
 DEV float micro_pdf(const Bsdf &b, F3 wo, F3 wi) {
     if (!same_hemisphere(wo, wi)) return 0;
     F3 wh = normalize(wo + wi);
     return tr_pdf(wo, wh, b.alpha, b.alpha_y) / (4 * dot(wo, wh));
+}
+// FresnelBlend::f, reflection.cpp:285-298, and its SchlickFresnel, reflection.h:485-488
+DEV float pow5(float v) { return (v * v) * (v * v) * v; }
+DEV F3 blend_f(const Bsdf &b, F3 wo, F3 wi) {
+    const F3 one = F3{1.f, 1.f, 1.f};
+    const F3 diffuse = (28.f / (23.f * kPi)) * b.kd * (one - b.ks) * (1 - pow5(1 - .5f * fabsf(wi.z))) * (1 - pow5(1 - .5f * fabsf(wo.z)));
+    F3 wh = wi + wo;
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return F3{0, 0, 0};
+    wh = normalize(wh);
+    const float s = tr_d(wh, b.alpha, b.alpha_y) / (4 * absdot(wi, wh) * mx(fabsf(wi.z), fabsf(wo.z)));
+    const F3 schlick = b.ks + pow5(1 - dot(wi, wh)) * (one - b.ks);
+    return diffuse + s * schlick;
+}
+// FresnelBlend::Pdf, reflection.cpp:470-475
+DEV float blend_pdf(const Bsdf &b, F3 wo, F3 wi) {
+    if (!same_hemisphere(wo, wi)) return 0;
+    const F3 wh = normalize(wo + wi);
+    const float pdf_wh = tr_pdf(wo, wh, b.alpha, b.alpha_y);
+    return .5f * (fabsf(wi.z) * kInvPi + pdf_wh / (4 * dot(wo, wh)));
 }
 // LambertianReflection::f (reflection.cpp:178-180) or OrenNayar::f (reflection.cpp:197-219)
 DEV F3 diffuse_f(const Bsdf &b, F3 wo, F3 wi) {
@@ -1950,6 +2015,7 @@ DEV F3 lobes_f(const Bsdf &b, F3 wo, F3 wi) {
     F3 f = F3{0, 0, 0};
     if (b.has_lambert) f = f + diffuse_f(b, wo, wi);
     if (b.has_micro) f = f + micro_f(b, wo, wi);
+    if (b.has_blend) f = f + blend_f(b, wo, wi);
     return f;
 }
 // BSDF::f, reflection.cpp:686-699
@@ -1969,6 +2035,7 @@ DEV float bsdf_pdf(const Bsdf &b, F3 woW, F3 wiW) {
     if (b.has_lambert) pdf += lambert_pdf(wo, wi);
     if (b.has_micro) pdf += micro_pdf(b, wo, wi);
     if (b.has_mtrans) pdf += mtrans_pdf(b, wo, wi);
+    if (b.has_blend) pdf += blend_pdf(b, wo, wi);
     const int matching = n_nonspec(b);  // flags = BSDF_ALL & ~BSDF_SPECULAR
     return matching > 0 ? pdf / matching : 0.f;
 }
@@ -1987,6 +2054,7 @@ DEV F3 bsdf_sample_f(const Bsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *
     int comp = int(floorf(u0 * matching));
     if (comp > matching - 1) comp = matching - 1;
     // the comp-th present lobe in BxDF order: [3 uber's pass-through], 0 Lambertian, 1 microfacet, 2 specular reflection, [4 uber's Kt lobe]
+    // (6: substrate's FresnelBlend, the one lobe of its BSDF)
     int pick, count = comp;
     if (allow_specular && b.has_t0 && count-- == 0)
         pick = 3;
@@ -1996,6 +2064,8 @@ DEV F3 bsdf_sample_f(const Bsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *
         pick = 1;
     else if (b.has_mtrans && count-- == 0)
         pick = 5;   // rough glass: MicrofacetTransmission behind MicrofacetReflection (glass.cpp:74-90)
+    else if (b.has_blend && count-- == 0)
+        pick = 6;
     else if (!(allow_specular && b.has_t1) || (b.has_spec && count-- == 0))
         pick = 2;
     else
@@ -2022,6 +2092,20 @@ DEV F3 bsdf_sample_f(const Bsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *
             *pdf = tr_pdf(wo, wh, b.alpha, b.alpha_y) / (4 * dot(wo, wh));
             f = micro_f(b, wo, wi);
         }
+    } else if (pick == 6) {  // FresnelBlend::Sample_f, reflection.cpp:450-468
+        float ua = ur0;
+        if (ua < .5f) {
+            ua = mn(2 * ua, kOneMinusEpsilon);
+            wi = cosine_sample_hemisphere(ua, u1);
+            if (wo.z < 0) wi.z *= -1;
+        } else {
+            ua = mn(2 * (ua - .5f), kOneMinusEpsilon);
+            const F3 wh = tr_sample_wh(wo, ua, u1, b.alpha, b.alpha_y);
+            wi = -wo + 2 * dot(wo, wh) * wh;
+            if (!same_hemisphere(wo, wi)) return F3{0, 0, 0};  // `return Spectrum(0.f)`, pdf stays 0
+        }
+        *pdf = blend_pdf(b, wo, wi);
+        f = blend_f(b, wo, wi);
     } else if (pick == 5) {  // MicrofacetTransmission::Sample_f, reflection.cpp:425-433
         const F3 wh = tr_sample_wh(wo, ur0, u1, b.alpha, b.alpha_y);
         const float eta_a = 1.f, eta_b = b.eta;
@@ -2088,7 +2172,7 @@ DEV F3 bsdf_sample_f(const Bsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *
         return F3{0, 0, 0};
     }
     *wiW = to_world(b, wi);
-    const bool glossy = pick < 2 || pick == 5;
+    const bool glossy = pick < 2 || pick == 5 || pick == 6;
     if (glossy && matching > 1) {  // a specular lobe's Pdf() and f() are 0
         if (pick != 0 && b.has_lambert) *pdf += lambert_pdf(wo, wi);
         if (pick != 1 && b.has_micro) *pdf += micro_pdf(b, wo, wi);

@@ -33,7 +33,7 @@ struct DQuadric {
     float radius, inner_radius, height, zmin, zmax, phi_max;
     int reverse_orientation, swaps_handedness;
 };
-enum { kMatMatte = 0, kMatPlastic = 1, kMatUber = 2, kMatMirror = 3, kMatGlass = 4 };  // = IILE_MAT_* (checked in api.hip)
+enum { kMatMatte = 0, kMatPlastic = 1, kMatUber = 2, kMatMirror = 3, kMatGlass = 4, kMatMetal = 5, kMatSubstrate = 6 };  // = IILE_MAT_* (checked in api.hip)
 // (16-byte aligned, and the fields every hit reads first: (type, kd) and (ks, alpha) are one float4 each, see make_bsdf)
 struct alignas(16) DMaterial {
     int type;
@@ -49,9 +49,10 @@ struct alignas(16) DMaterial {
     int sigma_tex;                       // float image texture for matte's "sigma" (Oren-Nayar A, B per hit), or -1
     int rough_tex, remap_roughness;      // float image texture for "roughness" (-1: the constant alpha), RoughnessToAlpha or not
     float opacity[3];                    // uber: "opacity" ({1, 1, 1} otherwise)
-    float alpha_y;                       // uber, glass: the distribution's alpha along v ("vroughness"); = alpha otherwise
+    float alpha_y;                       // uber, glass, metal, substrate: the distribution's alpha along v ("vroughness"); = alpha otherwise
     int opacity_tex;                     // uber: image texture for "opacity" (times the constant), or -1
-    int rough_tex_v;                     // uber: -1 alpha_y is the constant, -2 alpha_y = the hit's alpha, >= 0 float image for "vroughness"
+    int rough_tex_v;                     // uber, metal, substrate: -1 alpha_y is the constant, -2 alpha_y = the hit's alpha, >= 0 float image for "vroughness"
+    float cond_eta[3], cond_k[3];        // metal: FresnelConductor(1, eta, k); 0 otherwise
 };
 // ImageTexture + MIPMap (iile_texture): level l holds w x h float4 texels (rgb, w unused) at
 // texels[offset[l] + t * w + s], row 0 = bottom scanline

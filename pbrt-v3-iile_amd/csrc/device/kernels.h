@@ -204,7 +204,7 @@ void launch_halton(const DScene &S, int n, const int *px, const int *py, const i
 void launch_camera(const DScene &S, int n, const float *pfilm, const float *plens, float *o, float *d,
                    const LaunchCfg &cfg);
 void launch_bsdf_probe(const DScene &S, int n, int mat, const float *wo, const float *wi_or_u, int sample,
-                       float *out, const LaunchCfg &cfg);
+                       float *out, const float ng[3], const LaunchCfg &cfg);
 void launch_trig_probe(int n, const float *x, float *out, const LaunchCfg &cfg);
 // one pass's flagged samples -> entries (after the pass's k_film_accumulate); all entries -> film (after k_film_resolve)
 void launch_patch_pass(const DScene &S, const PassDesc &P, const PassBuffers &B, const FilmBuffers &F, const PatchDev &D, const LaunchCfg &cfg);

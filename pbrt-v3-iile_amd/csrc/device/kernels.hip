@@ -502,14 +502,15 @@ __global__ void k_camera(DScene S, int n, const float *pfilm, const float *plens
     d[3 * i + 1] = rd.y;
     d[3 * i + 2] = rd.z;
 }
-// BSDF in a canonical frame (ns = ng = +z, ss = +x). sample == 0: out = {f.xyz, pdf}
+// BSDF in a canonical frame (ns = +z, ss = +x; the geometric normal ng, +z unless a test tilts it). sample == 0: out = {f.xyz, pdf}
 // for (wo, wi); sample == 1: out = {wi.xyz, f.xyz, pdf} for (wo, u).
-__global__ void k_bsdf_probe(DScene S, int n, int mat, const float *wo, const float *wi_or_u, int sample, float *out) {
+__global__ void k_bsdf_probe(DScene S, int n, int mat, const float *wo, const float *wi_or_u, int sample, float *out, float ngx,
+                             float ngy, float ngz) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Isect is;
     is.sn = F3{0, 0, 1};
-    is.n = F3{0, 0, 1};
+    is.n = F3{ngx, ngy, ngz};
     is.sdpdu = F3{1, 0, 0};
     is.p = is.perr = is.wo = F3{0, 0, 0};
     Bsdf b = make_bsdf(S.materials[mat], is);
@@ -602,9 +603,9 @@ void launch_camera(const DScene &S, int n, const float *pfilm, const float *plen
     hipLaunchKernelGGL(k_camera, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, pfilm, plens, o, d);
 }
 void launch_bsdf_probe(const DScene &S, int n, int mat, const float *wo, const float *wi_or_u, int sample,
-                       float *out, const LaunchCfg &cfg) {
+                       float *out, const float ng[3], const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_bsdf_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, mat, wo, wi_or_u, sample,
-                       out);
+                       out, ng[0], ng[1], ng[2]);
 }
 // ImageTexture::Evaluate for given (u, v) and differentials (test probe)
 __global__ void k_texture_probe(DScene S, int n, int tex, const float *uv, const float *duv, float *out) {

@@ -127,6 +127,15 @@ int iile_host_scene_quadric(const iile_host_scene *scene, int32_t index, iile_qu
     return 0;
 }
 
+int iile_host_scene_material(const iile_host_scene *scene, int32_t index, iile_material *out) {
+    if (!scene || !out || index < 0 || size_t(index) >= scene->s.materials.size()) {
+        g_err = "iile_host_scene_material: null argument or material index out of range";
+        return 1;
+    }
+    *out = scene->s.materials[size_t(index)];
+    return 0;
+}
+
 void iile_host_scene_free(iile_host_scene *scene) { delete scene; }
 
 int iile_host_sobol_matrices(int32_t n_dims, uint32_t *m32, uint64_t *m64) {

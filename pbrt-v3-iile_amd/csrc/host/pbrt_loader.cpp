@@ -766,6 +766,25 @@ class Loader {
         return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
     }
     int make_material(const std::string &name, const ParamSet &ps_in) {
+        if (name == "metal") {  // "eta" / "k": rgb, color or a constant named texture; what else pbrt-v3 takes is refused by name
+            for (const char *param : {"eta", "k"}) {
+                const Param *p = ps_in.find(param);
+                if (!p) continue;
+                if (p->type == "spectrum" || p->type == "blackbody") {
+                    fail(std::string("Material \"metal\": parameter \"") + param + "\" given as \"" + p->type +
+                         "\" is not supported (rgb, color or a constant texture)");
+                    return -1;
+                }
+                if (p->type == "texture" && p->strs.size() == 1) {
+                    auto it = gs_.textures.find(p->strs[0]);
+                    if (it != gs_.textures.end() && it->second.image >= 0) {
+                        fail(std::string("Material \"metal\": parameter \"") + param + "\" given as the image texture \"" + p->strs[0] +
+                             "\" is not supported (rgb, color or a constant texture)");
+                        return -1;
+                    }
+                }
+            }
+        }
         ParamSet ps;
         std::map<std::string, int> image_of;
         if (!resolve_textures(ps_in, &ps, &image_of)) return -1;
@@ -846,14 +865,44 @@ class Loader {
             float kr[3] = {0.9f, 0.9f, 0.9f};
             ps.rgb("Kr", kr);
             for (int i = 0; i < 3; ++i) m.kr[i] = kr[i];
+        } else if (name == "metal") {  // CreateMetalMaterial, metal.cpp:104-127
+            m.type = IILE_MAT_METAL;
+            // RGBSpectrum::FromSampled(CopperWavelengths, CopperN / CopperK, CopperSamples) (metal.cpp:108-116), worked out in float64
+            // from the reference's tables and rounded to float (tests/golden/make_copper_fixture.py, copper_fixture.json)
+            float eta[3] = {0.199989721f, 0.922085762f, 1.09987628f}, k[3] = {3.90463829f, 2.44763327f, 2.13765097f};
+            ps.rgb("eta", eta);
+            ps.rgb("k", k);
+            for (int i = 0; i < 3; ++i) m.cond_eta[i] = eta[i], m.cond_k[i] = k[i];
+            // uRough = uRoughness ? uRoughness : roughness, vRough = vRoughness ? vRoughness : roughness (metal.cpp:68-71): each
+            // falls back to "roughness" on its own (images: below)
+            const float r = ps.one_float("roughness", .01f);
+            m.roughness = ps.one_float("uroughness", r);
+            m.roughness_v = ps.one_float("vroughness", r);
+            m.rough_tex_v = -1;
+            m.remap_roughness = ps.one_bool("remaproughness", true) ? 1 : 0;
+            m.alpha = m.remap_roughness ? roughness_to_alpha(m.roughness) : m.roughness;
+            m.alpha_v = m.remap_roughness ? roughness_to_alpha(m.roughness_v) : m.roughness_v;
+        } else if (name == "substrate") {  // CreateSubstrateMaterial, substrate.cpp:81-96
+            m.type = IILE_MAT_SUBSTRATE;
+            float kd[3] = {.5f, .5f, .5f}, ks[3] = {.5f, .5f, .5f};
+            ps.rgb("Kd", kd);
+            ps.rgb("Ks", ks);
+            for (int i = 0; i < 3; ++i) m.kd[i] = kd[i], m.ks[i] = ks[i];
+            // "uroughness" / "vroughness", each .1 by default; "roughness" is not looked at
+            m.roughness = ps.one_float("uroughness", .1f);
+            m.roughness_v = ps.one_float("vroughness", .1f);
+            m.rough_tex_v = -1;
+            m.remap_roughness = ps.one_bool("remaproughness", true) ? 1 : 0;
+            m.alpha = m.remap_roughness ? roughness_to_alpha(m.roughness) : m.roughness;
+            m.alpha_v = m.remap_roughness ? roughness_to_alpha(m.roughness_v) : m.roughness_v;
         } else {
-            fail("Material \"" + name + "\" is not supported (matte, plastic, uber, mirror, glass)");
+            fail("Material \"" + name + "\" is not supported (matte, plastic, uber, mirror, glass, metal, substrate)");
             return -1;
         }
         // which parameters each material looks up (an image given for one it does not have is ignored, as a
         // constant would be)
-        if (m.type == IILE_MAT_MATTE || m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER) m.kd_tex = image("Kd");
-        if (m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER) m.ks_tex = image("Ks");
+        if (m.type == IILE_MAT_MATTE || m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER || m.type == IILE_MAT_SUBSTRATE) m.kd_tex = image("Kd");
+        if (m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER || m.type == IILE_MAT_SUBSTRATE) m.ks_tex = image("Ks");
         if (m.type == IILE_MAT_UBER || m.type == IILE_MAT_MIRROR || m.type == IILE_MAT_GLASS) m.kr_tex = image("Kr");
         if (m.type == IILE_MAT_GLASS || m.type == IILE_MAT_UBER) m.kt_tex = image("Kt");
         if (m.type == IILE_MAT_UBER) m.opacity_tex = image("opacity");   // GetSpectrumTexture("opacity", 1.f), uber.cpp:117
@@ -865,22 +914,31 @@ class Loader {
                 }
                 m.sigma_tex = image("sigma");
             }
-        {   // float images for the roughness parameters: "roughness" (plastic, uber), "uroughness" / "vroughness" (uber)
+        {   // float images for the roughness parameters: "roughness" (plastic, uber, metal), "uroughness" / "vroughness" (uber, metal,
+            // substrate; substrate ignores "roughness", substrate.cpp:88-91)
             const Param *rp = ps.find("roughness"), *up = ps.find("uroughness"), *vp = ps.find("vroughness");
             const bool r_img = rp && rp->type == "roughimage", u_img = up && up->type == "roughimage", v_img = vp && vp->type == "roughimage";
-            if ((r_img && m.type != IILE_MAT_PLASTIC && m.type != IILE_MAT_UBER) || ((u_img || v_img) && m.type != IILE_MAT_UBER)) {
-                fail("roughness: a float \"imagemap\" texture is supported on plastic (\"roughness\") and uber (\"roughness\", \"uroughness\", \"vroughness\") only");
+            const bool uv_mat = m.type == IILE_MAT_UBER || m.type == IILE_MAT_METAL || m.type == IILE_MAT_SUBSTRATE;
+            if ((r_img && m.type != IILE_MAT_PLASTIC && m.type != IILE_MAT_UBER && m.type != IILE_MAT_METAL && m.type != IILE_MAT_SUBSTRATE) ||
+                ((u_img || v_img) && !uv_mat)) {
+                fail("roughness: a float \"imagemap\" texture is supported on plastic (\"roughness\"), uber and metal (\"roughness\", "
+                     "\"uroughness\", \"vroughness\") and substrate (\"uroughness\", \"vroughness\") only");
                 return -1;
             }
-            // roughu = roughnessu ? roughnessu : roughness (uber.cpp:79-82): "roughness" is not looked at when "uroughness" is there
-            if (m.type == IILE_MAT_UBER && up)
+            if (m.type == IILE_MAT_METAL) {  // metal.cpp:68-71: each of u and v is its own parameter if given, else "roughness"
+                m.rough_tex = up ? (u_img ? image("uroughness") : -1) : (r_img ? image("roughness") : -1);
+                m.rough_tex_v = vp ? (v_img ? image("vroughness") : -1) : (r_img ? image("roughness") : -1);
+            } else if (m.type == IILE_MAT_SUBSTRATE) {
+                m.rough_tex = u_img ? image("uroughness") : -1;
+                m.rough_tex_v = v_img ? image("vroughness") : -1;
+            } else if (m.type == IILE_MAT_UBER && up)  // roughu = roughnessu ? roughnessu : roughness (uber.cpp:79-82): "roughness" is not looked at when "uroughness" is there
                 m.rough_tex = u_img ? image("uroughness") : -1;
             else if (r_img)
                 m.rough_tex = image("roughness");
         }
         if (const Param *bp = ps.find("bumpmap")) {  // GetFloatTextureOrNull("bumpmap") of every material's Create*
             if (bp->type != "bumpimage" || m.type == IILE_MAT_GLASS) {
-                fail("bumpmap: only a float \"imagemap\" texture on matte / plastic / uber / mirror is supported");
+                fail("bumpmap: only a float \"imagemap\" texture on matte / plastic / uber / mirror / metal / substrate is supported");
                 return -1;
             }
             m.bump_tex = image("bumpmap");
