@@ -303,6 +303,9 @@ int32_t iile_wide_ref_shift(void);
 /* ImageTexture<RGBSpectrum, Spectrum>::Evaluate (src/textures/imagemap.h:87-94) of image texture `tex` at n
  * surface points given by (u, v) and the screen-space differentials {du/dx, dv/dx, du/dy, dv/dy}. */
 int iile_texture_eval(iile_scene *scene, int32_t tex, int32_t n, const float *uv2, const float *duv4, float *rgb3);
+/* Texture::Evaluate of texture `tex` of any kind (image or procedural, include/iile_scene.h) at n surface points: (u, v), the
+ * differentials {du/dx, dv/dx, du/dy, dv/dy} and pdp9 = {p, dp/dx, dp/dy} (9 floats per point) */
+int iile_texture_eval_p(iile_scene *scene, int32_t tex, int32_t n, const float *uv2, const float *duv4, const float *pdp9, float *rgb3);
 /* portable sin / cos / acos used on the device: out[3i..] = {sin x, cos x, acos clamp(x)} */
 int iile_trig_probe(int32_t n, const float *x, float *out3);
 

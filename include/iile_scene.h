@@ -152,7 +152,28 @@ typedef struct iile_texture {
     float su, sv, du, dv; /* UVMapping2D */
     int32_t level_w[IILE_MAX_TEX_LEVELS], level_h[IILE_MAX_TEX_LEVELS];
     int64_t level_offset[IILE_MAX_TEX_LEVELS]; /* in texels */
+    /* Procedural textures (everything below is zero for an image entry, whose kind is then IILE_TEX_IMAGE). A procedural entry has
+     * n_levels = 0 and no texels. The tree has two levels at most: a combiner (scale, mix, or a checkerboard with a non-constant
+     * input) over leaves (an image, uv, bilerp, a checkerboard of constants); constant subtrees are folded by the loader. */
+    int32_t kind;    /* IILE_TEX_* */
+    int32_t mapping; /* the 2D classes: IILE_MAP_* (TextureMapping2D, src/core/texture.h:51-112). uv: su, sv, du, dv above;
+                        planar: vs, vt with ds, dt in du, dv */
+    float vs[3], vt[3];
+    /* row-major 3x4 (an affine CTM: the loader refuses a projective one). spherical / cylindrical: Inverse(tex2world), their
+     * WorldToTexture; checkerboard dimension 3: tex2world itself, which CreateCheckerboard*Texture hands to IdentityMapping3D as its
+     * WorldToTexture (textures/checkerboard.cpp:91,149) */
+    float xf[12];
+    /* inputs: scale tex1, tex2; mix tex1, tex2, amount; checkerboard tex1, tex2: a texture index (a leaf), or -1 for the constant in
+     * cval (a float input holds its value in all three channels) */
+    int32_t child[3];
+    float cval[3][3];
+    int32_t aamode;      /* checkerboard dimension 2: IILE_AA_* */
+    float bilerp[4][3];  /* bilerp: v00, v01, v10, v11 */
 } iile_texture;
+enum { IILE_TEX_IMAGE = 0, IILE_TEX_SCALE = 1, IILE_TEX_MIX = 2, IILE_TEX_CHECKER2D = 3, IILE_TEX_CHECKER3D = 4, IILE_TEX_UV = 5,
+       IILE_TEX_BILERP = 6 };
+enum { IILE_MAP_UV = 0, IILE_MAP_SPHERICAL = 1, IILE_MAP_CYLINDRICAL = 2, IILE_MAP_PLANAR = 3 };
+enum { IILE_AA_CLOSEDFORM = 0, IILE_AA_NONE = 1 };
 
 /* A light: DiffuseAreaLight on a shape (src/lights/diffuse.h:48-75) or one of the delta lights
  * PointLight (src/lights/point.h:49-70), SpotLight (src/lights/spot.h:49-74), DistantLight

@@ -46,7 +46,16 @@ class Texture(ctypes.Structure):
     """iile_texture (include/iile_scene.h)."""
     _fields_ = [("n_levels", c_i32), ("wrap", c_i32), ("trilinear", c_i32), ("max_aniso", c_f32), ("su", c_f32),
                 ("sv", c_f32), ("du", c_f32), ("dv", c_f32), ("level_w", c_i32 * 16), ("level_h", c_i32 * 16),
-                ("level_offset", ctypes.c_int64 * 16)]
+                ("level_offset", ctypes.c_int64 * 16),
+                # procedural textures (all zero for an image): appended, include/iile_scene.h
+                ("kind", c_i32), ("mapping", c_i32), ("vs", c_f32 * 3), ("vt", c_f32 * 3), ("xf", c_f32 * 12), ("child", c_i32 * 3),
+                ("cval", (c_f32 * 3) * 3), ("aamode", c_i32), ("bilerp", (c_f32 * 3) * 4)]
+
+
+# iile_texture::kind, ::mapping, ::aamode
+TEX_IMAGE, TEX_SCALE, TEX_MIX, TEX_CHECKER2D, TEX_CHECKER3D, TEX_UV, TEX_BILERP = range(7)
+MAP_UV, MAP_SPHERICAL, MAP_CYLINDRICAL, MAP_PLANAR = range(4)
+AA_CLOSEDFORM, AA_NONE = range(2)
 
 
 class Light(ctypes.Structure):
@@ -154,7 +163,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
-               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_trig_probe", "iile_texture_eval", "iile_render_probes",
+               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_render_probes",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
                "iile_iispt_film_add", "iile_iispt_film_merge",
@@ -270,6 +279,7 @@ def gpu_lib():
         lib.iile_li_samples.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         lib.iile_bsdf_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_texture_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
+        lib.iile_texture_eval_p.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_render_probes.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, ctypes.POINTER(GpuStats), c_vp]
         lib.iile_bsdf_sample.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_bsdf_eval_ng.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
@@ -513,6 +523,15 @@ class HostScene:
             levels.append(a)
         return t, levels
 
+    def procedural_texture(self, index):
+        """The fields of texture `index` as a dict: kind, mapping and its data, inputs (-1: the constant), aamode, bilerp corners.
+        An image entry has kind TEX_IMAGE and zeros elsewhere."""
+        t, _ = self.texture(index)
+        return {"kind": t.kind, "mapping": t.mapping, "n_levels": t.n_levels, "su": t.su, "sv": t.sv, "du": t.du, "dv": t.dv,
+                "vs": list(t.vs), "vt": list(t.vt), "xf": np.array(list(t.xf), np.float32).reshape(3, 4),
+                "child": list(t.child), "cval": np.array([list(r) for r in t.cval], np.float32), "aamode": t.aamode,
+                "bilerp": np.array([list(r) for r in t.bilerp], np.float32)}
+
     @property
     def film_filename(self):
         """The scene file's Film "filename"."""
@@ -751,6 +770,15 @@ class GpuScene:
         out = np.empty((len(uv), 3), np.float32)
         self._check(gpu_lib().iile_texture_eval(self._s, tex, len(uv), uv.ctypes.data, duv.ctypes.data, out.ctypes.data),
                     "iile_texture_eval")
+        return out
+
+    def texture_eval_p(self, tex, uv, duv, p, dpdx, dpdy):
+        """Texture::Evaluate of any texture at (n, 2) uv, (n, 4) {dudx, dvdx, dudy, dvdy}, (n, 3) p, dpdx, dpdy -> (n, 3)."""
+        uv, duv = _f32(uv), _f32(duv)
+        pdp = np.ascontiguousarray(np.concatenate([_f32(p), _f32(dpdx), _f32(dpdy)], axis=1), np.float32)
+        out = np.empty((len(uv), 3), np.float32)
+        self._check(gpu_lib().iile_texture_eval_p(self._s, tex, len(uv), uv.ctypes.data, duv.ctypes.data, pdp.ctypes.data,
+                                                  out.ctypes.data), "iile_texture_eval_p")
         return out
 
     def bsdf_sample(self, mat, wo, u):

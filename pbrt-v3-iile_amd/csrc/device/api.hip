@@ -812,6 +812,8 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
                 masks[i] = make_int2(d->prim_alpha[2 * i], d->prim_alpha[2 * i + 1]);
                 for (int m : {masks[i].x, masks[i].y})
                     if (m >= d->n_textures || m < IILE_ALPHA_ZERO) return bail(fail(IILE_ERR_ARG, "alpha mask refers to a texture that does not exist"));
+                    else if (m >= 0 && d->textures[m].kind != IILE_TEX_IMAGE)  // (the traversal kernels look up images only)
+                        return bail(fail(IILE_ERR_ARG, "alpha mask refers to a procedural texture"));
             }
             rc = upload(sc, masks.data(), masks.size(), &S.prim_alpha);
             if (rc) return bail(rc);
@@ -918,7 +920,30 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
             std::vector<DTexture> tx(d->n_textures);
             for (int i = 0; i < d->n_textures; ++i) {
                 const iile_texture &t = d->textures[i];
-                if (t.n_levels < 1 || t.n_levels > kMaxTexLevels) return bail(fail(IILE_ERR_ARG, "texture with a bad level count"));
+                if (t.kind < IILE_TEX_IMAGE || t.kind > IILE_TEX_BILERP) return bail(fail(IILE_ERR_ARG, "texture of an unknown kind"));
+                if ((t.kind == IILE_TEX_IMAGE && (t.n_levels < 1 || t.n_levels > kMaxTexLevels)) || (t.kind != IILE_TEX_IMAGE && t.n_levels != 0))
+                    return bail(fail(IILE_ERR_ARG, "texture with a bad level count"));
+                tx[i].kind = t.kind;
+                tx[i].mapping = t.mapping;
+                tx[i].aamode = t.aamode;
+                std::memcpy(tx[i].vs, t.vs, sizeof(t.vs));
+                std::memcpy(tx[i].vt, t.vt, sizeof(t.vt));
+                std::memcpy(tx[i].xf, t.xf, sizeof(t.xf));
+                std::memcpy(tx[i].cval, t.cval, sizeof(t.cval));
+                std::memcpy(tx[i].bilerp, t.bilerp, sizeof(t.bilerp));
+                for (int k = 0; k < 3; ++k) {
+                    // a combiner's input is a leaf (an image, uv, bilerp, or a checkerboard of constants): the device evaluates two
+                    // levels and does not recurse
+                    tx[i].child[k] = t.kind == IILE_TEX_IMAGE ? -1 : t.child[k];
+                    const int c = tx[i].child[k];
+                    if (c < -1 || c >= d->n_textures) return bail(fail(IILE_ERR_ARG, "texture input out of range"));
+                    if (c >= 0) {
+                        const iile_texture &ct = d->textures[c];
+                        const bool leaf = ct.kind == IILE_TEX_IMAGE || ct.kind == IILE_TEX_UV || ct.kind == IILE_TEX_BILERP ||
+                                          ((ct.kind == IILE_TEX_CHECKER2D || ct.kind == IILE_TEX_CHECKER3D) && ct.child[0] < 0 && ct.child[1] < 0);
+                        if (!leaf) return bail(fail(IILE_ERR_ARG, "texture input that is not a leaf (textures nest two levels deep at most)"));
+                    }
+                }
                 tx[i].n_levels = t.n_levels;
                 tx[i].wrap = t.wrap;
                 tx[i].trilinear = t.trilinear;
@@ -966,7 +991,7 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
             if (d->lights[i].type == IILE_LIGHT_INFINITE) {
                 S.has_infinite = 1;
                 const iile_light &il = d->lights[i];
-                if (il.env_tex < 0 || il.env_tex >= d->n_textures || il.dist_w < 1 || il.dist_h < 1 || il.dist_offset < 0 ||
+                if (il.env_tex < 0 || il.env_tex >= d->n_textures || d->textures[il.env_tex].kind != IILE_TEX_IMAGE || il.dist_w < 1 || il.dist_h < 1 || il.dist_offset < 0 ||
                     il.dist_offset + int64_t(2 * il.dist_w + 2) * il.dist_h + 2 * il.dist_h + 2 > d->n_env_dist)
                     return bail(fail(IILE_ERR_ARG, "infinite light: bad environment map / distribution reference"));
             }
@@ -2690,13 +2715,33 @@ int iile_texture_eval(iile_scene *sc, int32_t tex, int32_t n, const float *uv2, 
     int rc;
     if ((rc = duv.put(uv2, 2 * size_t(n))) || (rc = dd.put(duv4, 4 * size_t(n))) || (rc = dout.alloc(3 * size_t(n)))) return rc;
     LaunchCfg cfg{sc->n_cus, nullptr, false};
-    if (n) launch_texture_probe(sc->ds, n, tex, duv.p, dd.p, dout.p, cfg);
+    if (n) launch_texture_probe(sc->ds, n, tex, duv.p, dd.p, nullptr, dout.p, cfg);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return dout.get(rgb3, 3 * size_t(n));
+}
+
+int iile_texture_eval_p(iile_scene *sc, int32_t tex, int32_t n, const float *uv2, const float *duv4, const float *pdp9, float *rgb3) {
+    if (!sc || n < 0 || !uv2 || !duv4 || !pdp9 || !rgb3 || tex < 0 || tex >= sc->ds.n_textures)
+        return fail(IILE_ERR_ARG, "iile_texture_eval_p: bad argument");
+    DevBuf<float> duv, dd, dp, dout;
+    int rc;
+    if ((rc = duv.put(uv2, 2 * size_t(n))) || (rc = dd.put(duv4, 4 * size_t(n))) || (rc = dp.put(pdp9, 9 * size_t(n))) ||
+        (rc = dout.alloc(3 * size_t(n))))
+        return rc;
+    LaunchCfg cfg{sc->n_cus, nullptr, false};
+    if (n) launch_texture_probe(sc->ds, n, tex, duv.p, dd.p, dp.p, dout.p, cfg);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return dout.get(rgb3, 3 * size_t(n));
 }
 
 static_assert(kShapeHitFloats == IILE_SHAPE_HIT_FLOATS, "shape hit record");
+static_assert(kTexImage == IILE_TEX_IMAGE && kTexScale == IILE_TEX_SCALE && kTexMix == IILE_TEX_MIX && kTexChecker2D == IILE_TEX_CHECKER2D &&
+                  kTexChecker3D == IILE_TEX_CHECKER3D && kTexUV == IILE_TEX_UV && kTexBilerp == IILE_TEX_BILERP && kMapUV == IILE_MAP_UV &&
+                  kMapSpherical == IILE_MAP_SPHERICAL && kMapCylindrical == IILE_MAP_CYLINDRICAL && kMapPlanar == IILE_MAP_PLANAR &&
+                  kAAClosedForm == IILE_AA_CLOSEDFORM && kAANone == IILE_AA_NONE,
+              "texture kinds");
 int iile_shape_hit_attributes(iile_scene *sc, int32_t n, const float *o3, const float *d3, const int32_t *prim, float *out) {
     if (!sc || n < 0 || !o3 || !d3 || !prim || !out) return fail(IILE_ERR_ARG, "iile_shape_hit_attributes: bad argument");
     for (int32_t i = 0; i < n; ++i)  // sphere and quadric primitives only: their flag word has bit 0 (api.hip, the vertex records)

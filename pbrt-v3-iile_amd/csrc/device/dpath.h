@@ -1300,7 +1300,14 @@ DEV void trav_step(const DScene &S, Trav &t, const StackRef &sr, TraceStats *st)
 struct TexDiff {
     float dudx, dvdx, dudy, dvdy;
 };
-DEV F3 tex_evaluate(const DScene &S, int tex, float u, float v, const TexDiff &td);  // defined with the textures below
+DEV F3 tex_image(const DScene &S, int tex, float u, float v, const TexDiff &td);  // defined with the textures below
+// where a texture is evaluated: SurfaceInteraction's uv, p and their screen-space differentials (dpdx / dpdy: zero where the
+// caller's (u, v) differentials are zero)
+struct TexCtx {
+    float u, v;
+    TexDiff td;
+    F3 p, dpdx, dpdy;
+};
 
 // The alpha test of Triangle::Intersect / IntersectP (triangle.cpp:325-331, 509-541) on a hit that passed the
 // geometric test: isectLocal carries uvHit and zero differentials, so an ImageTexture<Float, Float> filters
@@ -1316,10 +1323,10 @@ DEV bool alpha_rejects(const DScene &S, int prim, uint32_t flags, float b0, floa
     const int2 masks = S.prim_alpha[prim];
     const TexDiff zero = TexDiff{0, 0, 0, 0};
     if (masks.x == -2) return true;  // IILE_ALPHA_ZERO
-    if (masks.x >= 0 && tex_evaluate(S, masks.x, u, v, zero).x == 0) return true;
+    if (masks.x >= 0 && tex_image(S, masks.x, u, v, zero).x == 0) return true;
     if (any_hit) {
         if (masks.y == -2) return true;
-        if (masks.y >= 0 && tex_evaluate(S, masks.y, u, v, zero).x == 0) return true;
+        if (masks.y >= 0 && tex_image(S, masks.y, u, v, zero).x == 0) return true;
     }
     return false;
 }
@@ -1585,7 +1592,7 @@ DEV F3 tex_ewa(const DScene &S, const DTexture &t, int level, float st0, float s
     }
     return F3{sum.x / sum_wts, sum.y / sum_wts, sum.z / sum_wts};
 }
-DEV F3 tex_evaluate(const DScene &S, int tex, float u, float v, const TexDiff &td) {
+DEV F3 tex_image(const DScene &S, int tex, float u, float v, const TexDiff &td) {
     const DTexture &t = S.textures[tex];
     float d00 = t.su * td.dudx, d01 = t.sv * td.dvdx, d10 = t.su * td.dudy, d11 = t.sv * td.dvdy;
     const float st0 = t.su * u + t.du, st1 = t.sv * v + t.dv;
@@ -1615,16 +1622,181 @@ DEV F3 tex_evaluate(const DScene &S, int tex, float u, float v, const TexDiff &t
     return lerp_f3(lod - float(ilod), tex_ewa(S, t, ilod, st0, st1, d00, d01, d10, d11),
                    tex_ewa(S, t, ilod + 1, st0, st1, d00, d01, d10, d11));
 }
+// ===========================================================================
+// procedural textures (src/textures/checkerboard.h, uv.h, bilerp.h, scale.h, mix.h) over the mappings of src/core/texture.cpp.
+// No recursion and no runtime-indexed arrays: a combiner (scale, mix, a checkerboard with a non-constant input) evaluates its
+// inputs, each a leaf (an image, uv, bilerp, a checkerboard of constants), into named registers (the loader and the upload keep
+// trees to these two levels)
+// ===========================================================================
+// (s, t) and its differentials: TextureMapping2D::Map
+struct TexSt {
+    float s, t, dsdx, dtdx, dsdy, dtdy;
+};
+DEV F3 tex_xf_point(const DTexture &t, F3 p) {  // Transform::operator()(Point3f) of an affine 3 x 4 (transform.h:217-232)
+    return F3{t.xf[0] * p.x + t.xf[1] * p.y + t.xf[2] * p.z + t.xf[3], t.xf[4] * p.x + t.xf[5] * p.y + t.xf[6] * p.z + t.xf[7],
+              t.xf[8] * p.x + t.xf[9] * p.y + t.xf[10] * p.z + t.xf[11]};
+}
+// SphericalMapping2D::sphere / CylindricalMapping2D::cylinder (texture.cpp:119-123, texture.h:92-95)
+DEV void tex_sph_cyl(const DTexture &t, bool sph, F3 p, float *s, float *tt) {
+    const F3 vec = normalize(tex_xf_point(t, p));
+    const float phi = atan2_f(vec.y, vec.x);
+    if (sph) {
+        const float theta = acos_f(clampf(vec.z, -1, 1));  // SphericalTheta, SphericalPhi (geometry.h)
+        *s = theta * kInvPi;
+        *tt = (phi < 0 ? phi + 2 * kPi : phi) * kInv2Pi;
+    } else {
+        *s = (kPi + phi) * kInv2Pi;
+        *tt = vec.z;
+    }
+}
+DEV float tex_wrap_dt(float d) {  // the sphere / cylinder mapping's discontinuity fix-up of dt (texture.cpp:108-116, 133-141)
+    if (d > .5f) return 1.f - d;
+    if (d < -.5f) return -(d + 1);
+    return d;
+}
+// diffs: whether the differentials are wanted (only the closed-form checkerboard reads them)
+DEV TexSt tex_map2d(const DTexture &t, const TexCtx &c, bool diffs) {
+    TexSt r = TexSt{0, 0, 0, 0, 0, 0};
+    if (t.mapping == kMapUV) {  // UVMapping2D::Map, texture.cpp:93-99
+        r.dsdx = t.su * c.td.dudx, r.dtdx = t.sv * c.td.dvdx;
+        r.dsdy = t.su * c.td.dudy, r.dtdy = t.sv * c.td.dvdy;
+        r.s = t.su * c.u + t.du, r.t = t.sv * c.v + t.dv;
+    } else if (t.mapping == kMapPlanar) {  // PlanarMapping2D::Map, texture.cpp:147-153
+        const F3 vs = F3{t.vs[0], t.vs[1], t.vs[2]}, vt = F3{t.vt[0], t.vt[1], t.vt[2]};
+        r.dsdx = dot(c.dpdx, vs), r.dtdx = dot(c.dpdx, vt);
+        r.dsdy = dot(c.dpdy, vs), r.dtdy = dot(c.dpdy, vt);
+        r.s = t.du + dot(c.p, vs), r.t = t.dv + dot(c.p, vt);
+    } else {  // SphericalMapping2D::Map (delta .1), CylindricalMapping2D::Map (delta .01), texture.cpp:101-145
+        const bool sph = t.mapping == kMapSpherical;
+        const float delta = sph ? .1f : .01f;
+        // one copy of the mapping for the point and its two offsets
+#pragma nounroll
+        for (int k = 0; k < (diffs ? 3 : 1); ++k) {
+            const F3 q = k == 0 ? c.p : c.p + delta * (k == 1 ? c.dpdx : c.dpdy);
+            float s, tt;
+            tex_sph_cyl(t, sph, q, &s, &tt);
+            if (k == 0)
+                r.s = s, r.t = tt;
+            else if (k == 1)
+                r.dsdx = s, r.dtdx = tt;
+            else
+                r.dsdy = s, r.dtdy = tt;
+        }
+        if (diffs) {
+            const float inv = 1 / delta;  // Vector2f::operator/
+            r.dsdx = (r.dsdx - r.s) * inv, r.dtdx = tex_wrap_dt((r.dtdx - r.t) * inv);
+            r.dsdy = (r.dsdy - r.s) * inv, r.dtdy = tex_wrap_dt((r.dtdy - r.t) * inv);
+        }
+    }
+    return r;
+}
+// Checkerboard2DTexture / Checkerboard3DTexture::Evaluate (checkerboard.h:65-103, 117-127) short of the lookups of tex1 / tex2:
+// 0 or 1: tex1 or tex2 alone; 2: (1 - *area2) * tex1 + *area2 * tex2. st: the 2D mapping (with differentials for the closed form)
+DEV int tex_checker(const DTexture &t, const TexCtx &c, const TexSt &st, float *area2) {
+    if (t.kind == kTexChecker3D) {  // IdentityMapping3D::Map (texture.cpp:155-160)
+        const F3 q = tex_xf_point(t, c.p);
+        return (int(floorf(q.x)) + int(floorf(q.y)) + int(floorf(q.z))) % 2 == 0 ? 0 : 1;
+    }
+    if (t.aamode == kAANone) return (int(floorf(st.s)) + int(floorf(st.t))) % 2 == 0 ? 0 : 1;
+    const float ds = mx(fabsf(st.dsdx), fabsf(st.dsdy)), dt = mx(fabsf(st.dtdx), fabsf(st.dtdy));
+    const float s0 = st.s - ds, s1 = st.s + ds, t0 = st.t - dt, t1 = st.t + dt;
+    if (floorf(s0) == floorf(s1) && floorf(t0) == floorf(t1)) return (int(floorf(st.s)) + int(floorf(st.t))) % 2 == 0 ? 0 : 1;
+    auto bump_int = [](float x) { return float(int(floorf(x / 2))) + 2 * mx(x / 2 - float(int(floorf(x / 2))) - .5f, 0.f); };
+    const float sint = (bump_int(s1) - bump_int(s0)) / (2 * ds), tint = (bump_int(t1) - bump_int(t0)) / (2 * dt);
+    float a2 = sint + tint - 2 * sint * tint;
+    if (ds > 1 || dt > 1) a2 = .5f;
+    *area2 = a2;
+    return 2;
+}
+DEV F3 tex_blend(float a2, F3 a, F3 b) {  // (1 - area2) * tex1 + area2 * tex2
+    return F3{(1 - a2) * a.x + a2 * b.x, (1 - a2) * a.y + a2 * b.y, (1 - a2) * a.z + a2 * b.z};
+}
+DEV F3 tex_cval(const DTexture &t, int k) { return F3{t.cval[k][0], t.cval[k][1], t.cval[k][2]}; }
+// a leaf that is not an image: uv (UVTexture, uv.h:54-60), bilerp (BilerpTexture, bilerp.h:56-62), a checkerboard of constants
+DEV F3 tex_proc_leaf(const DTexture &t, const TexCtx &c) {
+    TexSt st = TexSt{0, 0, 0, 0, 0, 0};
+    if (t.kind != kTexChecker3D) st = tex_map2d(t, c, t.kind == kTexChecker2D && t.aamode == kAAClosedForm);
+    if (t.kind == kTexUV) return F3{st.s - floorf(st.s), st.t - floorf(st.t), 0};
+    if (t.kind == kTexBilerp) {
+        const float a = (1 - st.s) * (1 - st.t), b = (1 - st.s) * st.t, d = st.s * (1 - st.t), e = st.s * st.t;
+        return F3{a * t.bilerp[0][0] + b * t.bilerp[1][0] + d * t.bilerp[2][0] + e * t.bilerp[3][0],
+                  a * t.bilerp[0][1] + b * t.bilerp[1][1] + d * t.bilerp[2][1] + e * t.bilerp[3][1],
+                  a * t.bilerp[0][2] + b * t.bilerp[1][2] + d * t.bilerp[2][2] + e * t.bilerp[3][2]};
+    }
+    float a2 = 0;
+    const int sel = tex_checker(t, c, st, &a2);
+    return sel == 0 ? tex_cval(t, 0) : (sel == 1 ? tex_cval(t, 1) : tex_blend(a2, tex_cval(t, 0), tex_cval(t, 1)));
+}
+DEV F3 tex_leaf(const DScene &S, int tex, const TexCtx &c) {
+    const DTexture &t = S.textures[tex];
+    if (t.kind == kTexImage) return tex_image(S, tex, c.u, c.v, c.td);
+    return tex_proc_leaf(t, c);
+}
+// a procedural texture (kind != kTexImage)
+DEV F3 tex_procedural(const DScene &S, int tex, const TexCtx &c) {
+    const DTexture &t = S.textures[tex];
+    const bool checker = t.kind == kTexChecker2D || t.kind == kTexChecker3D;
+    const bool combiner = t.kind == kTexScale || t.kind == kTexMix || (checker && (t.child[0] >= 0 || t.child[1] >= 0));
+    if (!combiner) return tex_leaf(S, tex, c);
+    // the combination as a sum (mix, checkerboard: w0 * in0 + w1 * in1, the inputs a checkerboard does not select left out, as
+    // Evaluate leaves them) or a product (scale: in0 * in1), accumulated input by input: the same roundings as the reference's
+    // expressions (0 + x and 1 * x are exact), with one value held instead of three
+    float w0 = 1, w1 = 1;
+    int need = 3;
+    if (checker) {
+        TexSt st = TexSt{0, 0, 0, 0, 0, 0};
+        if (t.kind == kTexChecker2D) st = tex_map2d(t, c, t.aamode == kAAClosedForm);
+        float a2 = 0;
+        const int sel = tex_checker(t, c, st, &a2);
+        if (sel == 2)
+            w0 = 1 - a2, w1 = a2;
+        else
+            need = 1 << sel;
+    }
+    const bool prod = t.kind == kTexScale;  // ScaleTexture, scale.h:56-58
+    F3 acc = prod ? F3{1, 1, 1} : F3{0, 0, 0};
+    // MixTexture (mix.h:57-61): (1 - amt) * tex1 + amt * tex2, its amount (a float texture) looked up first
+    const bool mix = t.kind == kTexMix;
+#pragma nounroll
+    for (int i = mix ? -1 : 0; i < 2; ++i) {  // one copy of the leaf code
+        const int k = i < 0 ? 2 : i;
+        if (k < 2 && !((need >> k) & 1)) continue;
+        const int ch = t.child[k];
+        const F3 r = ch < 0 ? tex_cval(t, k) : tex_leaf(S, ch, c);
+        if (k == 2)
+            w0 = 1 - r.x, w1 = r.x;
+        else if (prod)
+            acc = acc * r;
+        else if (need != 3)
+            acc = r;  // a checkerboard's selection
+        else {
+            const float w = k == 0 ? w0 : w1;
+            acc = F3{acc.x + w * r.x, acc.y + w * r.y, acc.z + w * r.z};
+        }
+    }
+    return acc;
+}
+// Texture::Evaluate(si) of any texture of the scene
+DEV F3 tex_evaluate(const DScene &S, int tex, const TexCtx &c) {
+    if (S.textures[tex].kind == kTexImage) return tex_image(S, tex, c.u, c.v, c.td);  // ImageTexture over UVMapping2D, as it always was
+    return tex_procedural(S, tex, c);
+}
+DEV TexCtx tex_ctx(const Isect &is, const TexDiff &td, F3 dpdx, F3 dpdy) { return TexCtx{is.u, is.v, td, is.p, dpdx, dpdy}; }
+
 // Material::Bump (material.cpp:45-86) with an ImageTexture<Float, Float> displacement, then
 // SetShadingGeometry(dpdu, dpdv, dndu, dndv, false) (interaction.cpp:72-92)
-DEV void bump(const DScene &S, int tex, const TexDiff &td, Isect *is) {
+DEV void bump(const DScene &S, int tex, const TexDiff &td, F3 dpdx, F3 dpdy, Isect *is) {
+    TexCtx c = tex_ctx(*is, td, dpdx, dpdy);
     float du = .5f * (fabsf(td.dudx) + fabsf(td.dudy));
     if (du == 0) du = .0005f;
-    const float u_displace = tex_evaluate(S, tex, is->u + du, is->v + 0.f, td).x;
+    c.u = is->u + du, c.v = is->v + 0.f, c.p = is->p + du * is->sdpdu;  // siEval.p = p + du * shading.dpdu, siEval.uv = uv + (du, 0)
+    const float u_displace = tex_evaluate(S, tex, c).x;
     float dv = .5f * (fabsf(td.dvdx) + fabsf(td.dvdy));
     if (dv == 0) dv = .0005f;
-    const float v_displace = tex_evaluate(S, tex, is->u + 0.f, is->v + dv, td).x;
-    const float displace = tex_evaluate(S, tex, is->u, is->v, td).x;
+    c.u = is->u + 0.f, c.v = is->v + dv, c.p = is->p + dv * is->sdpdv;
+    const float v_displace = tex_evaluate(S, tex, c).x;
+    c.u = is->u, c.v = is->v, c.p = is->p;
+    const float displace = tex_evaluate(S, tex, c).x;
     const F3 dpdu = is->sdpdu + (u_displace - displace) / du * is->sn + displace * is->dndu;
     const F3 dpdv = is->sdpdv + (v_displace - displace) / dv * is->sn + displace * is->dndv;
     F3 sn = normalize(cross(dpdu, dpdv));
@@ -1636,22 +1808,23 @@ DEV void bump(const DScene &S, int tex, const TexDiff &td, Isect *is) {
 }
 
 // the material with its textured parameters looked up at the hit (Texture::Evaluate(*si))
-DEV DMaterial textured_material(const DScene &S, const DMaterial &m, const Isect &is, const TexDiff &td) {
+DEV DMaterial textured_material(const DScene &S, const DMaterial &m, const Isect &is, const TexDiff &td, F3 dpdx, F3 dpdy) {
     DMaterial r = m;
+    const TexCtx tc = tex_ctx(is, td, dpdx, dpdy);
     if (m.kd_tex >= 0) {
-        const F3 c = tex_evaluate(S, m.kd_tex, is.u, is.v, td);  // times the constant: 1, or a "scale" texture's factor
+        const F3 c = tex_evaluate(S, m.kd_tex, tc);  // times the constant: 1, or a "scale" texture's factor
         r.kd[0] = c.x * m.kd[0], r.kd[1] = c.y * m.kd[1], r.kd[2] = c.z * m.kd[2];
     }
     if (m.ks_tex >= 0) {
-        const F3 c = tex_evaluate(S, m.ks_tex, is.u, is.v, td);  // times the constant: 1, or a "scale" texture's factor
+        const F3 c = tex_evaluate(S, m.ks_tex, tc);  // times the constant: 1, or a "scale" texture's factor
         r.ks[0] = c.x * m.ks[0], r.ks[1] = c.y * m.ks[1], r.ks[2] = c.z * m.ks[2];
     }
     if (m.kr_tex >= 0) {
-        const F3 c = tex_evaluate(S, m.kr_tex, is.u, is.v, td);  // times the constant: 1, or a "scale" texture's factor
+        const F3 c = tex_evaluate(S, m.kr_tex, tc);  // times the constant: 1, or a "scale" texture's factor
         r.kr[0] = c.x * m.kr[0], r.kr[1] = c.y * m.kr[1], r.kr[2] = c.z * m.kr[2];
     }
     if (m.sigma_tex >= 0) {  // sigma->Evaluate(*si), matte.cpp:56-61; OrenNayar's constants, reflection.h:414-420
-        const float sig = clampf(tex_evaluate(S, m.sigma_tex, is.u, is.v, td).x, 0.f, 90.f);
+        const float sig = clampf(tex_evaluate(S, m.sigma_tex, tc).x, 0.f, 90.f);
         r.on_a = 1.f;
         r.on_b = 0.f;
         if (sig != 0) {
@@ -1662,7 +1835,7 @@ DEV DMaterial textured_material(const DScene &S, const DMaterial &m, const Isect
         }
     }
     if (m.rough_tex >= 0) {  // roughness->Evaluate(*si), then RoughnessToAlpha (microfacet.h:123-128)
-        float rough = tex_evaluate(S, m.rough_tex, is.u, is.v, td).x;
+        float rough = tex_evaluate(S, m.rough_tex, tc).x;
         if (m.remap_roughness) {
             rough = mx(rough, 1e-3f);
             const float x = log_f(rough);
@@ -1672,7 +1845,7 @@ DEV DMaterial textured_material(const DScene &S, const DMaterial &m, const Isect
         if (m.rough_tex_v == -2) r.alpha_y = rough;   // roughv = roughu, uber.cpp:83-84 (plastic: one roughness)
     }
     if (m.rough_tex_v >= 0) {  // "vroughness" as a float image (uber.cpp:76, 83)
-        float rough = tex_evaluate(S, m.rough_tex_v, is.u, is.v, td).x;
+        float rough = tex_evaluate(S, m.rough_tex_v, tc).x;
         if (m.remap_roughness) {
             rough = mx(rough, 1e-3f);
             const float x = log_f(rough);
@@ -1681,11 +1854,11 @@ DEV DMaterial textured_material(const DScene &S, const DMaterial &m, const Isect
         r.alpha_y = rough;
     }
     if (m.opacity_tex >= 0) {  // opacity->Evaluate(*si), uber.cpp:53
-        const F3 c = tex_evaluate(S, m.opacity_tex, is.u, is.v, td);
+        const F3 c = tex_evaluate(S, m.opacity_tex, tc);
         r.opacity[0] = c.x * m.opacity[0], r.opacity[1] = c.y * m.opacity[1], r.opacity[2] = c.z * m.opacity[2];
     }
     if (m.kt_tex >= 0) {
-        const F3 c = tex_evaluate(S, m.kt_tex, is.u, is.v, td);  // times the constant: 1, or a "scale" texture's factor
+        const F3 c = tex_evaluate(S, m.kt_tex, tc);  // times the constant: 1, or a "scale" texture's factor
         r.kt[0] = c.x * m.kt[0], r.kt[1] = c.y * m.kt[1], r.kt[2] = c.z * m.kt[2];
     }
     return r;

@@ -63,7 +63,18 @@ struct DTexture {
     float max_aniso, su, sv, du, dv;
     int level_w[kMaxTexLevels], level_h[kMaxTexLevels];
     long long level_offset[kMaxTexLevels];
+    // procedural textures (iile_texture): kind 0 is an image, whose remaining fields are unused
+    int kind, mapping;
+    float vs[3], vt[3];
+    float xf[12];
+    int child[3];
+    float cval[3][3];
+    int aamode;
+    float bilerp[4][3];
 };
+enum { kTexImage = 0, kTexScale = 1, kTexMix = 2, kTexChecker2D = 3, kTexChecker3D = 4, kTexUV = 5, kTexBilerp = 6 };  // = IILE_TEX_*
+enum { kMapUV = 0, kMapSpherical = 1, kMapCylindrical = 2, kMapPlanar = 3 };                                          // = IILE_MAP_*
+enum { kAAClosedForm = 0, kAANone = 1 };                                                                               // = IILE_AA_*
 enum { kLightDiffuseArea = 0, kLightPoint = 1, kLightSpot = 2, kLightDistant = 3, kLightAreaTriangle = 4,
        kLightInfinite = 5, kLightAreaQuadric = 6 };  // = IILE_LIGHT_* (checked in api.hip)
 struct DLight {

@@ -85,10 +85,11 @@ DEV void vertex_state(const DScene &S, const float4 o4, const float4 d4, const f
     if (S.textured_materials &&
         (m0.kd_tex >= 0 || m0.ks_tex >= 0 || m0.kr_tex >= 0 || m0.kt_tex >= 0 || m0.bump_tex >= 0 || m0.rough_tex >= 0 || m0.sigma_tex >= 0 || m0.opacity_tex >= 0 || m0.rough_tex_v >= 0)) {
         TexDiff td = TexDiff{0, 0, 0, 0};
+        F3 dpdx = F3{0, 0, 0}, dpdy = F3{0, 0, 0};
         // only the camera ray carries differentials (r.ScaleDifferentials(1.0): S.diff_scale is 1 in these kernels)
-        if (camera_ray_hit) td = compute_differentials(*is, camera_differentials(S, pf4.x, pf4.y, pf4.z, pf4.w, ro, rd));
-        if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, is);
-        const DMaterial mm = textured_material(S, m0, *is, td);
+        if (camera_ray_hit) td = compute_differentials(*is, camera_differentials(S, pf4.x, pf4.y, pf4.z, pf4.w, ro, rd), &dpdx, &dpdy);
+        if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, is);
+        const DMaterial mm = textured_material(S, m0, *is, td, dpdx, dpdy);
         *bsdf = make_bsdf<true>(mm, *is);
     } else {
         *bsdf = make_bsdf<true>(m0, *is);
@@ -228,7 +229,9 @@ DEV void iispt_aux_ray(const Isect &is, F3 ray_d, F3 *o, F3 *d) {
 }
 }  // namespace
 
-__global__ __launch_bounds__(kIisptBlock) void k_iispt_hemi_out(DScene S, const IisptJob *jobs) {
+// (waves_per_eu 4: the parent's occupancy, which the procedural textures' branch of vertex_state would otherwise lower to 3; it fits
+//  in 128 VGPRs without scratch)
+__global__ __launch_bounds__(kIisptBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_iispt_hemi_out(DScene S, const IisptJob *jobs) {
     const IisptItems I = jobs[blockIdx.y].I;
     uint8_t *valid = jobs[blockIdx.y].valid;
     float *pos3 = jobs[blockIdx.y].pos3, *dir3 = jobs[blockIdx.y].dir3;

@@ -213,7 +213,8 @@ void launch_patch_own(const DScene &S, const float4 *L, int n, const uint32_t *l
                       int kc, float4 *out, const LaunchCfg &cfg);
 void launch_gather4(const float4 *src, const uint32_t *idx, int n, float4 *out, const LaunchCfg &cfg);
 void launch_scatter4(float4 *dst, const uint32_t *idx, int n, const float4 *in, const LaunchCfg &cfg);
-void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, float *out, const LaunchCfg &cfg);
+void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, const float *pdp, float *out,
+                          const LaunchCfg &cfg);
 constexpr int kShapeHitFloats = 28;  // = IILE_SHAPE_HIT_FLOATS
 void launch_shape_hit_probe(const DScene &S, int n, const float *o, const float *d, const int *prim, float *out, const LaunchCfg &cfg);
 

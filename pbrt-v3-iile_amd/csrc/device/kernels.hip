@@ -607,15 +607,21 @@ void launch_bsdf_probe(const DScene &S, int n, int mat, const float *wo, const f
     hipLaunchKernelGGL(k_bsdf_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, mat, wo, wi_or_u, sample,
                        out, ng[0], ng[1], ng[2]);
 }
-// ImageTexture::Evaluate for given (u, v) and differentials (test probe)
-__global__ void k_texture_probe(DScene S, int n, int tex, const float *uv, const float *duv, float *out) {
+// Texture::Evaluate for given (u, v) and differentials and, if pdp is not null, p, dpdx and dpdy (9 floats per point; else
+// zero) (test probe)
+__global__ void k_texture_probe(DScene S, int n, int tex, const float *uv, const float *duv, const float *pdp, float *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const TexDiff td = TexDiff{duv[4 * i], duv[4 * i + 1], duv[4 * i + 2], duv[4 * i + 3]};
-    const F3 c = tex_evaluate(S, tex, uv[2 * i], uv[2 * i + 1], td);
-    out[3 * i] = c.x;
-    out[3 * i + 1] = c.y;
-    out[3 * i + 2] = c.z;
+    TexCtx c = TexCtx{uv[2 * i], uv[2 * i + 1], TexDiff{duv[4 * i], duv[4 * i + 1], duv[4 * i + 2], duv[4 * i + 3]}, F3{0, 0, 0},
+                      F3{0, 0, 0}, F3{0, 0, 0}};
+    if (pdp) {
+        const float *q = pdp + 9 * size_t(i);
+        c.p = F3{q[0], q[1], q[2]}, c.dpdx = F3{q[3], q[4], q[5]}, c.dpdy = F3{q[6], q[7], q[8]};
+    }
+    const F3 v = tex_evaluate(S, tex, c);
+    out[3 * i] = v.x;
+    out[3 * i + 1] = v.y;
+    out[3 * i + 2] = v.z;
 }
 // The SurfaceInteraction of a sphere or quadric hit (shape_hit_interaction<DIFFS = true>) for ray i and the primitive its closest
 // hit found (the caller checked that it is not a triangle): kShapeHitFloats floats per ray, see iile_shape_hit_attributes
@@ -636,8 +642,9 @@ __global__ void k_shape_hit_probe(DScene S, int n, const float *o, const float *
 void launch_shape_hit_probe(const DScene &S, int n, const float *o, const float *d, const int *prim, float *out, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_shape_hit_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, o, d, prim, out);
 }
-void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, float *out, const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_texture_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, tex, uv, duv, out);
+void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, const float *pdp, float *out,
+                          const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_texture_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, tex, uv, duv, pdp, out);
 }
 __global__ void k_gather4(const float4 *src, const uint32_t *idx, int n, float4 *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -293,8 +293,8 @@ __global__ __launch_bounds__(kBlock, IILE_DIRECT_SHADE_WAVES) void k_direct_shad
                 if (has_diff) td = compute_differentials(is, rdiff, &dpdx, &dpdy);
             }
             if (TEX && S.textured_materials && mat_tex) {
-                if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, &is);
-                bsdf = make_bsdf<true>(textured_material(S, m0, is, td), is);
+                if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, &is);
+                bsdf = make_bsdf<true>(textured_material(S, m0, is, td, dpdx, dpdy), is);
             } else {
                 bsdf = make_bsdf<true>(m0, is);
             }
@@ -516,12 +516,12 @@ TREE_CALL void tree_interaction(const DScene &S, int prim, F3 ro, F3 rd, float b
     }
 }
 template <bool TEX>
-TREE_CALL void tree_bsdf(const DScene &S, int material, const TexDiff &td, Isect *is, Bsdf *bsdf) {
+TREE_CALL void tree_bsdf(const DScene &S, int material, const TexDiff &td, F3 dpdx, F3 dpdy, Isect *is, Bsdf *bsdf) {
     const DMaterial &m0 = S.materials[material];
     const bool mat_tex = m0.kd_tex >= 0 || m0.ks_tex >= 0 || m0.kr_tex >= 0 || m0.kt_tex >= 0 || m0.bump_tex >= 0 || m0.rough_tex >= 0 || m0.sigma_tex >= 0 || m0.opacity_tex >= 0 || m0.rough_tex_v >= 0;
     if (TEX && S.textured_materials && mat_tex) {
-        if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, is);
-        *bsdf = make_bsdf<true>(textured_material(S, m0, *is, td), *is);
+        if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, is);
+        *bsdf = make_bsdf<true>(textured_material(S, m0, *is, td, dpdx, dpdy), *is);
     } else {
         *bsdf = make_bsdf<true>(m0, *is);
     }
@@ -612,7 +612,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_direct_tree(DScene S, PassDesc P,
                 F3 dpdx = F3{0, 0, 0}, dpdy = F3{0, 0, 0};
                 if (TEX && has_diff) td = compute_differentials(is, rdiff, &dpdx, &dpdy);
                 Bsdf bsdf;
-                tree_bsdf<TEX>(S, material, td, &is, &bsdf);
+                tree_bsdf<TEX>(S, material, td, dpdx, dpdy, &is, &bsdf);
                 TreeLevel<NT> &me = lv[depth];
                 me.L = F3{0, 0, 0};
                 if (light >= 0) me.L = me.L + area_light_L(S.lights[light], is.n, -rd);  // L += isect.Le(wo)

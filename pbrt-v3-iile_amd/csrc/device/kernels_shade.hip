@@ -334,6 +334,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                         const DMaterial &m0 = S.materials[material];
                         if (m0.kd_tex >= 0 || m0.ks_tex >= 0 || m0.kr_tex >= 0 || m0.kt_tex >= 0 || m0.bump_tex >= 0 || m0.rough_tex >= 0 || m0.sigma_tex >= 0 || m0.opacity_tex >= 0 || m0.rough_tex_v >= 0) {
                             TexDiff td = TexDiff{0, 0, 0, 0};
+                            F3 dpdx = F3{0, 0, 0}, dpdy = F3{0, 0, 0};
                             if (bounce == 0) {
                                 int px = 0, py = 0;
                                 uint32_t kk = 0;
@@ -348,10 +349,10 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                                     S.probe_mode ? probe_differentials(S, P.probe_cams[(pid / uint32_t(P.kc)) / (256u * uint32_t(P.probe_tiles))],
                                                                        float(px) + u0, float(py) + u1, ray_o, ray_d)
                                                  : camera_differentials(S, float(px) + u0, float(py) + u1, l0, l1, ray_o, ray_d);
-                                td = compute_differentials(is, rdiff);
+                                td = compute_differentials(is, rdiff, &dpdx, &dpdy);
                             }
-                            if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, &is);  // `if (bumpMap) Bump(bumpMap, si)` comes first
-                            const DMaterial mm = textured_material(S, m0, is, td);
+                            if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, &is);  // `if (bumpMap) Bump(bumpMap, si)` comes first
+                            const DMaterial mm = textured_material(S, m0, is, td, dpdx, dpdy);
                             bsdf = make_bsdf<EXT>(mm, is);
                         } else {
                             bsdf = make_bsdf<EXT>(m0, is);

@@ -184,6 +184,9 @@ struct ConstTexture {
     float v[3] = {0, 0, 0};
     int image = -1;  // an "imagemap" spectrum texture: index into HostScene::textures (not constant: kept by reference)
     bool scaled = false;  // a "scale" of that image with a constant: v is the constant factor
+    // `image` is a texture of any kind (iile_texture::kind). leaf: an image, uv, bilerp or checkerboard of constants, which a
+    // combiner may take as an input; a combiner (and an (image, factor) pair) is not one
+    bool leaf = true;
 };
 struct GraphicsState {
     int material = -1;  // index into scene->materials, -1 = default matte
@@ -645,6 +648,9 @@ class Loader {
             const Param *p = ps.find(names[k]);
             if (!p || p->type != "texture" || p->strs.size() != 1) continue;
             auto it = gs_.textures.find(p->strs[0]);
+            if (it != gs_.textures.end() && it->second.image >= 0 && !it->second.is_float &&
+                scene_->textures[size_t(it->second.image)].t.kind != IILE_TEX_IMAGE)
+                return false;  // a procedural input: a combiner, not this fold
             if (it == gs_.textures.end() || it->second.image < 0 || it->second.is_float || it->second.scaled) continue;
             if (which >= 0) return false;  // two images: not folded
             which = k;
@@ -662,7 +668,82 @@ class Loader {
         }
         for (int i = 0; i < 3; ++i) t->v[i] = c[i];
         t->scaled = true;
+        t->leaf = false;  // a combination (image times factor): a combiner over it would be a third level, and would drop the factor
         return true;
+    }
+    // an input of a procedural texture (TextureParams::GetFloatTexture / GetSpectrumTexture): a constant (given directly, a
+    // constant named texture, or the default) goes to *val with *idx = -1; a named leaf texture gives its index
+    bool tex_input(const std::string &tex_name, const ParamSet &ps, const std::string &name, bool want_float, const float def[3],
+                   int *idx, float val[3]) {
+        *idx = -1;
+        const Param *p = ps.find(name);
+        if (p && p->type == "texture" && p->strs.size() == 1) {
+            auto it = gs_.textures.find(p->strs[0]);
+            if (it != gs_.textures.end() && it->second.is_float == want_float && it->second.image >= 0) {
+                if (!it->second.leaf)
+                    return fail("Texture \"" + tex_name + "\": input \"" + name + "\" is \"" + p->strs[0] +
+                                "\", itself a combination of textures; textures nest two levels deep at most");
+                *idx = it->second.image;
+                for (int i = 0; i < 3; ++i) val[i] = 0.f;
+                return true;
+            }
+        }
+        return tex_value(ps, name, want_float, def, val);
+    }
+    // TextureParams::FindVector3f (a "vector" / "vector3" parameter of three numbers)
+    static V3 find_vector(const ParamSet &ps, const std::string &name, V3 def) {
+        const Param *p = ps.find(name);
+        if (p && p->type == "vector" && p->nums.size() == 3) return V3(float(p->nums[0]), float(p->nums[1]), float(p->nums[2]));
+        return def;
+    }
+    // the upper 3 x 4 of an affine matrix (the bottom row (0, 0, 0, 1))
+    bool affine_3x4(const Mat4 &m, const std::string &tex_name, float out[12]) {
+        if (m.m[3][0] != 0.f || m.m[3][1] != 0.f || m.m[3][2] != 0.f || m.m[3][3] != 1.f)
+            return fail("Texture \"" + tex_name + "\": a projective texture transform is not supported");
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) out[4 * r + c] = m.m[r][c];
+        return true;
+    }
+    // the TextureMapping2D of the 2D classes (checkerboard.cpp:55-76 and the same code in uv.cpp, bilerp.cpp)
+    bool mapping_2d(const std::string &tex_name, const ParamSet &ps, iile_texture *t) {
+        const std::string type = ps.one_string("mapping", "uv");
+        t->su = 1.f, t->sv = 1.f, t->du = 0.f, t->dv = 0.f;
+        if (type == "uv") {
+            t->mapping = IILE_MAP_UV;
+            t->su = ps.one_float("uscale", 1.f);
+            t->sv = ps.one_float("vscale", 1.f);
+            t->du = ps.one_float("udelta", 0.f);
+            t->dv = ps.one_float("vdelta", 0.f);
+        } else if (type == "spherical" || type == "cylindrical") {  // Inverse(tex2world): the CTM's inverse
+            t->mapping = type == "spherical" ? IILE_MAP_SPHERICAL : IILE_MAP_CYLINDRICAL;
+            if (!affine_3x4(ctm_.inv, tex_name, t->xf)) return false;
+        } else if (type == "planar") {
+            t->mapping = IILE_MAP_PLANAR;
+            const V3 v1 = find_vector(ps, "v1", V3(1, 0, 0)), v2 = find_vector(ps, "v2", V3(0, 1, 0));
+            t->vs[0] = v1.x, t->vs[1] = v1.y, t->vs[2] = v1.z;
+            t->vt[0] = v2.x, t->vt[1] = v2.y, t->vt[2] = v2.z;
+            t->du = ps.one_float("udelta", 0.f);
+            t->dv = ps.one_float("vdelta", 0.f);
+        } else {  // Error(...) and a default UVMapping2D
+            std::fprintf(stderr, "Error: 2D texture mapping \"%s\" unknown\n", type.c_str());
+            t->mapping = IILE_MAP_UV;
+        }
+        return true;
+    }
+    // a procedural entry of HostScene::textures (n_levels = 0, no texels); t becomes a reference to it
+    void add_procedural(const iile_texture &pt, bool leaf, ConstTexture *t) {
+        HostTexture ht;
+        ht.t = pt;
+        scene_->textures.push_back(std::move(ht));
+        t->image = int(scene_->textures.size()) - 1;
+        t->leaf = leaf;
+    }
+    static iile_texture blank_texture(int kind) {
+        iile_texture pt;
+        std::memset(&pt, 0, sizeof(pt));
+        pt.kind = kind;
+        pt.child[0] = pt.child[1] = pt.child[2] = -1;
+        return pt;
     }
     bool make_texture(const std::string &name, const std::string &type, const std::string &cls, const ParamSet &ps) {
         const bool is_float = type == "float";
@@ -670,10 +751,76 @@ class Loader {
         const float zero[3] = {0, 0, 0}, one[3] = {1, 1, 1}, half[3] = {.5f, .5f, .5f};
         ConstTexture t;
         t.is_float = is_float;
+        // scale / mix with a texture among their inputs: a combiner entry (constant inputs fold below, as they always have)
+        auto has_texture_input = [&](std::initializer_list<std::pair<const char *, bool>> inputs) {
+            for (const auto &in : inputs) {
+                const Param *p = ps.find(in.first);
+                if (!p || p->type != "texture" || p->strs.size() != 1) continue;
+                auto it = gs_.textures.find(p->strs[0]);
+                if (it != gs_.textures.end() && it->second.is_float == in.second && it->second.image >= 0) return true;
+            }
+            return false;
+        };
         if (cls == "constant") {  // CreateConstant*Texture, textures/constant.cpp: "value" default 1
             if (!tex_value(ps, "value", is_float, one, t.v)) return false;
         } else if (cls == "scale" && !is_float && scale_of_image(ps, &t)) {
             // an image texture times a constant: kept as (image, factor); the product is taken at the hit
+        } else if ((cls == "scale" && has_texture_input({{"tex1", is_float}, {"tex2", is_float}})) ||
+                   (cls == "mix" && has_texture_input({{"tex1", is_float}, {"tex2", is_float}, {"amount", true}}))) {
+            // ScaleTexture / MixTexture over non-constant inputs (scale.cpp:42-53, mix.cpp:42-55): evaluated at the hit
+            const bool mix = cls == "mix";
+            iile_texture pt = blank_texture(mix ? IILE_TEX_MIX : IILE_TEX_SCALE);
+            if (!tex_input(name, ps, "tex1", is_float, mix ? zero : one, &pt.child[0], pt.cval[0]) ||
+                !tex_input(name, ps, "tex2", is_float, one, &pt.child[1], pt.cval[1]))
+                return false;
+            if (mix && !tex_input(name, ps, "amount", true, half, &pt.child[2], pt.cval[2])) return false;
+            add_procedural(pt, false, &t);
+        } else if (cls == "checkerboard") {  // CreateCheckerboard{Float,Spectrum}Texture, checkerboard.cpp:42-152
+            const int dim = ps.one_int("dimension", 2);
+            if (dim != 2 && dim != 3) return fail("Texture \"" + name + "\": " + std::to_string(dim) + " dimensional checkerboard texture not supported");
+            iile_texture pt = blank_texture(dim == 2 ? IILE_TEX_CHECKER2D : IILE_TEX_CHECKER3D);
+            const float tex2_def[3] = {0, 0, 0};
+            if (!tex_input(name, ps, "tex1", is_float, one, &pt.child[0], pt.cval[0]) ||
+                !tex_input(name, ps, "tex2", is_float, tex2_def, &pt.child[1], pt.cval[1]))
+                return false;
+            if (dim == 2) {
+                if (!mapping_2d(name, ps, &pt)) return false;
+                const std::string aa = ps.one_string("aamode", "closedform");
+                if (aa == "none")
+                    pt.aamode = IILE_AA_NONE;
+                else {
+                    if (aa != "closedform")
+                        std::fprintf(stderr, "Warning: Antialiasing mode \"%s\" not understood by Checkerboard2DTexture; using \"closedform\"\n",
+                                     aa.c_str());
+                    pt.aamode = IILE_AA_CLOSEDFORM;
+                }
+            } else if (!affine_3x4(ctm_.m, name, pt.xf))  // IdentityMapping3D(tex2world): tex2world is its WorldToTexture
+                return false;
+            add_procedural(pt, pt.child[0] < 0 && pt.child[1] < 0, &t);
+        } else if (cls == "uv" && is_float) {  // CreateUVFloatTexture returns no texture (uv.cpp:42-45)
+            return fail("Texture \"" + name + "\": class \"uv\" has no float version (a spectrum texture only)");
+        } else if (cls == "uv") {  // CreateUVSpectrumTexture, uv.cpp:47-74
+            iile_texture pt = blank_texture(IILE_TEX_UV);
+            if (!mapping_2d(name, ps, &pt)) return false;
+            add_procedural(pt, true, &t);
+        } else if (cls == "bilerp") {  // CreateBilerp{Float,Spectrum}Texture, bilerp.cpp:42-103: v00 0, v01 1, v10 0, v11 1
+            iile_texture pt = blank_texture(IILE_TEX_BILERP);
+            if (!mapping_2d(name, ps, &pt)) return false;
+            const char *corner[4] = {"v00", "v01", "v10", "v11"};
+            for (int k = 0; k < 4; ++k) {
+                const float d = (k & 1) ? 1.f : 0.f;
+                float c[3] = {d, d, d};
+                if (is_float) {
+                    c[0] = c[1] = c[2] = ps.one_float(corner[k], d);
+                } else
+                    ps.rgb(corner[k], c);
+                for (int i = 0; i < 3; ++i) pt.bilerp[k][i] = c[i];
+            }
+            add_procedural(pt, true, &t);
+        } else if (cls == "fbm" || cls == "wrinkled" || cls == "windy" || cls == "marble" || cls == "dots") {
+            return fail("Texture class \"" + cls + "\" is not supported (it needs pbrt's noise permutation table)");
+        } else if (cls == "ptex") {
+            return fail("Texture class \"ptex\" is not supported (it needs the Ptex library)");
         } else if (cls == "scale") {  // ScaleTexture::Evaluate = tex1 * tex2, textures/scale.h:56-58 (defaults 1, 1)
             float a[3], b[3];
             if (!tex_value(ps, "tex1", is_float, one, a) || !tex_value(ps, "tex2", is_float, one, b)) return false;
@@ -715,7 +862,7 @@ class Loader {
             scene_->textures.push_back(std::move(ht));
             t.image = int(scene_->textures.size()) - 1;
         } else
-            return fail("Texture class \"" + cls + "\" is not supported (constant, scale, mix of constants; imagemap)");
+            return fail("Texture class \"" + cls + "\" is not supported (constant, scale, mix, imagemap, checkerboard, uv, bilerp)");
         gs_.textures[name] = t;
         return true;
     }
@@ -1105,6 +1252,8 @@ class Loader {
                     auto it = gs_.textures.find(pa->strs[0]);
                     if (it == gs_.textures.end() || !it->second.is_float)
                         return fail("Couldn't find float texture \"" + pa->strs[0] + "\" for \"" + pnames[k] + "\" parameter");
+                    if (it->second.image >= 0 && scene_->textures[size_t(it->second.image)].t.kind != IILE_TEX_IMAGE)
+                        return fail("procedural texture \"" + pa->strs[0] + "\" as \"" + pnames[k] + "\" is not supported (image textures only)");
                     if (it->second.image >= 0)
                         alpha_mask[k] = it->second.image;
                     else if (it->second.v[0] == 0.f)
