@@ -28,6 +28,21 @@ extern "C" {
  *                          and oracle agree bit for bit. */
 enum { ORACLE_TRIG_LIBM = 0, ORACLE_TRIG_PORTABLE = 1 };
 
+/* Scene features the restatement does not cover. Every entry point that reads a scene checks it first and returns one of these,
+ * plus the feature's own enum value, instead of reading the scene through the wrong arrays:
+ *   PRIM     + IILE_PRIM_QUADRIC        a disk or a cylinder
+ *   LIGHT    + iile_light::type         an area light on a quadric
+ *   MATERIAL + iile_material::type      a material type outside matte .. substrate
+ *   TEXTURE  + iile_texture::kind       a procedural texture (anything but an image)
+ *   MAPPING  + iile_texture::mapping    a texture under a mapping other than uv (named before the texture's kind)
+ * The scene-wide entry points check the whole scene; the BSDF probes the material's type, oracle_texture_eval the texture, the
+ * ray queries the geometry. */
+#define ORACLE_UNSUPPORTED_PRIM 1000
+#define ORACLE_UNSUPPORTED_LIGHT 2000
+#define ORACLE_UNSUPPORTED_MATERIAL 3000
+#define ORACLE_UNSUPPORTED_TEXTURE 4000
+#define ORACLE_UNSUPPORTED_MAPPING 5000
+
 typedef struct oracle_stats {
     uint64_t camera_rays;      /* integrator.cpp:286 */
     uint64_t regular_rays;     /* Scene::Intersect calls, scene.cpp:45-50 */
@@ -75,25 +90,30 @@ void oracle_camera_ray(const iile_scene_desc *scene, float pfilm_x, float pfilm_
                        float plens_y, float *o3, float *d3);
 /* closest hit for n rays: prim[i] = -1 on miss; tb[4*i..] = {t, b0, b1, b2}
  * (for spheres b* are 0). */
-void oracle_intersect(const iile_scene_desc *scene, int n, const float *o, const float *d,
+int oracle_intersect(const iile_scene_desc *scene, int n, const float *o, const float *d,
                       const float *tmax, int32_t *prim, float *tb);
-void oracle_intersect_p(const iile_scene_desc *scene, int n, const float *o, const float *d,
+int oracle_intersect_p(const iile_scene_desc *scene, int n, const float *o, const float *d,
                         const float *tmax, int32_t *hit);
 /* Per-sample radiance Li for n (pixel, k) pairs; L: 3 floats each after the
  * NaN/negative/inf guards of integrator.cpp:293-314; nrays (optional): 2 per
  * sample {regular, shadow}. */
-void oracle_li(const iile_scene_desc *scene, int trig_mode, int n, const int32_t *px, const int32_t *py,
+int oracle_li(const iile_scene_desc *scene, int trig_mode, int n, const int32_t *px, const int32_t *py,
                const int32_t *k, float *L, int32_t *nrays);
 /* BSDF probes in the local shading frame of material `mat` with ns=ng=(0,0,1),
  * ss=(1,0,0): f (3), pdf and Sample_f -> {wi(3), f(3), pdf}. */
-void oracle_bsdf_eval(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3,
+int oracle_bsdf_eval(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3,
                       const float *wi3, float *f3, float *pdf);
-void oracle_bsdf_sample(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3,
+int oracle_bsdf_sample(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3,
                         const float *u2, float *wi3, float *f3, float *pdf);
+/* the same two with the geometric normal ng3 tilted off the shading normal +z (BSDF::f's reflect test reads ng) */
+int oracle_bsdf_eval_ng(const iile_scene_desc *scene, int trig_mode, int mat, const float *ng3, const float *wo3, const float *wi3,
+                        float *f3, float *pdf);
+int oracle_bsdf_sample_ng(const iile_scene_desc *scene, int trig_mode, int mat, const float *ng3, const float *wo3, const float *u2,
+                          float *wi3, float *f3, float *pdf);
 /* n samples / pdf evaluations for one outgoing direction (chi-square test of src/tests/bsdfs.cpp) */
-void oracle_bsdf_sample_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
+int oracle_bsdf_sample_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
                               const float *u2n, float *wi3n, float *pdfn);
-void oracle_bsdf_pdf_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
+int oracle_bsdf_pdf_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
                            const float *wi3n, float *pdfn);
 /* One IISPT probe: HemisphericCamera at `pos` looking along `dir` rendered by IISPTdIntegrator::RenderView
  * (iispt_d.cpp, hemispheric.cpp, iisptrenderrunner.cpp:316-346) with scene->probe's film / sampler / depth. Outputs
@@ -102,7 +122,7 @@ void oracle_bsdf_pdf_batch(const iile_scene_desc *scene, int trig_mode, int mat,
 int oracle_render_probe(const iile_scene_desc *scene, int trig_mode, const float *pos3, const float *dir3, float *intensity_rgb,
                         float *normals_xyz, float *distance);
 /* ImageTexture::Evaluate of texture `tex` at n (u, v) with differentials {dudx, dvdx, dudy, dvdy} */
-void oracle_texture_eval(const iile_scene_desc *scene, int trig_mode, int tex, int n, const float *uv2, const float *duv4,
+int oracle_texture_eval(const iile_scene_desc *scene, int trig_mode, int tex, int n, const float *uv2, const float *duv4,
                          float *rgb3);
 /* first hit of the camera ray through film point (pfx, pfy): {u, v, du/dx, dv/dx, du/dy, dv/dy} as
  * ComputeDifferentials leaves them (interaction.cpp:103-149); returns 0 when the ray escapes */
@@ -133,7 +153,7 @@ void oracle_sphere_solid_angle(const iile_scene_desc *scene, int sphere, const f
 /* Triangle.Sampling (shapes.cpp:210-271) for the area light `light` (a triangle or a sphere emitter):
  * the solid angle it subtends from p as sum 1 / (n pdf) over Shape::Sample(ref, u) with Halton (0, 1)
  * points, and by uniform-direction Monte Carlo with the same points. */
-void oracle_light_solid_angle(const iile_scene_desc *scene, int light, const float *p3, int n_samples,
+int oracle_light_solid_angle(const iile_scene_desc *scene, int light, const float *p3, int n_samples,
                               double *by_sampling, double *by_uniform_directions);
 int64_t oracle_check_next_float(int iters, uint64_t seed);
 int64_t oracle_check_efloat(int iters, uint64_t seed);

@@ -16,6 +16,10 @@
 //   EFloat, Quadratic                          core/efloat.h
 //   BSDF, Lambertian, MicrofacetReflection, TrowbridgeReitz, FrDielectric
 //                                              core/reflection.{h,cpp}, core/microfacet.cpp
+//   MetalMaterial, SubstrateMaterial, FrConductor, FresnelBlend
+//                                              materials/metal.cpp, materials/substrate.cpp, core/reflection.cpp
+// Not restated, and refused up front by every entry point that reads a scene (check_scene, oracle.h ORACLE_UNSUPPORTED_*):
+// disks and cylinders, procedural textures, texture mappings other than uv.
 //   DiffuseAreaLight, VisibilityTester, SpawnRay*, OffsetRayOrigin
 //   HaltonSampler / GlobalSampler / radical inverses
 //                                              samplers/halton.cpp, core/sampler.cpp, core/lowdiscrepancy.cpp
@@ -1556,8 +1560,14 @@ struct Oracle {
         // microfacet lobe above; MicrofacetTransmission(kt, distrib, 1, mt_eta, Radiance) — BSDF_TRANSMISSION | BSDF_GLOSSY: not specular
         bool has_mtrans = false;
         float mt_eta = 1.f;
+        // metal (metal.cpp:59-80): the microfacet lobe is MicrofacetReflection(1., distrib, FresnelConductor(1., eta, k)); ks is then
+        // Spectrum(1.) and the Fresnel term is FrConductor over the conductor's own eta and k
+        bool micro_conductor = false;
+        Rgb cond_eta, cond_k;
+        // substrate (substrate.cpp:45-65): FresnelBlend(Rd = kd, Rs = ks, TrowbridgeReitz(alpha, alpha_y)), BSDF_REFLECTION | BSDF_GLOSSY
+        bool has_blend = false;
         float eta = 1.f;                              // BSDF::eta (path.cpp:152)
-        int n_nonspec() const { return (has_lambert ? 1 : 0) + (has_micro ? 1 : 0) + (has_mtrans ? 1 : 0); }
+        int n_nonspec() const { return (has_lambert ? 1 : 0) + (has_micro ? 1 : 0) + (has_mtrans ? 1 : 0) + (has_blend ? 1 : 0); }
         V3 to_local(V3 v) const { return V3(dot(v, ss), dot(v, ts), dot(v, ns)); }
         V3 to_world(V3 v) const {
             return V3(ss.x * v.x + ts.x * v.y + ns.x * v.z, ss.y * v.x + ts.y * v.y + ns.y * v.z,
@@ -1606,6 +1616,42 @@ struct Oracle {
             Rgb v = tex_evaluate(tex, is) * Rgb(constant[0], constant[1], constant[2]);  // ScaleTexture: tex1 * tex2 (x 1 if plain)
             return clamp0(v.c);
         };
+        // roughness->Evaluate(*si) of a float image, then TrowbridgeReitzDistribution::RoughnessToAlpha if remapRoughness
+        // (microfacet.h:123-128)
+        auto rough_alpha = [&](int tex) {
+            float rough = tex_evaluate(tex, is).c[0];
+            if (m.remap_roughness) {
+                rough = std::max(rough, 1e-3f);
+                const float x = trig.log_f(rough);
+                rough = 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
+            }
+            return rough;
+        };
+        if (m.type == IILE_MAT_METAL) {  // MetalMaterial::ComputeScatteringFunctions, metal.cpp:59-80
+            // uRough = uRoughness ? uRoughness->Evaluate(*si) : roughness->Evaluate(*si), and likewise vRough (metal.cpp:67-70): the
+            // descriptor holds what each resolved to, a constant (alpha / alpha_v, remapped by the loader) or a float image
+            b.alpha = m.rough_tex >= 0 ? rough_alpha(m.rough_tex) : m.alpha;
+            b.alpha_y = m.rough_tex_v >= 0 ? rough_alpha(m.rough_tex_v) : m.alpha_v;
+            b.has_micro = true;
+            b.micro_conductor = true;
+            b.ks = Rgb(1.f);  // MicrofacetReflection's R: the `1.` of metal.cpp:79
+            b.cond_eta = Rgb(m.cond_eta[0], m.cond_eta[1], m.cond_eta[2]);  // eta->Evaluate(*si), k->Evaluate(*si): constants
+            b.cond_k = Rgb(m.cond_k[0], m.cond_k[1], m.cond_k[2]);
+            ++b.n_lobes;
+            return b;
+        }
+        if (m.type == IILE_MAT_SUBSTRATE) {  // SubstrateMaterial::ComputeScatteringFunctions, substrate.cpp:45-65
+            const Rgb d = param(m.kd, m.kd_tex), s = param(m.ks, m.ks_tex);  // Kd->Evaluate(*si).Clamp(), Ks->...
+            if (!d.is_black() || !s.is_black()) {
+                b.has_blend = true;
+                b.kd = d;
+                b.ks = s;
+                b.alpha = m.rough_tex >= 0 ? rough_alpha(m.rough_tex) : m.alpha;  // nu->Evaluate(*si), remapped
+                b.alpha_y = m.rough_tex_v >= 0 ? rough_alpha(m.rough_tex_v) : m.alpha_v;
+                ++b.n_lobes;
+            }
+            return b;
+        }
         // UberMaterial (uber.cpp:53-61): op = opacity.Clamp(), t = (-op + Spectrum(1.f)).Clamp(); a surface that is not opaque gets
         // BSDF(*si, 1.f) with SpecularTransmission(t, 1.f, 1.f, mode) as its first lobe, and every other coefficient is op * K.Clamp()
         Rgb op(1.f);
@@ -1764,6 +1810,31 @@ struct Oracle {
         float r_perp = ((eta_i * cos_i) - (eta_t * cos_t)) / ((eta_i * cos_i) + (eta_t * cos_t));
         return (r_parl * r_parl + r_perp * r_perp) / 2;
     }
+    // FrConductor (reflection.cpp:71-96) with etai = Spectrum(1.) (FresnelConductor(1., eta, k), metal.cpp:77-78), per channel in the
+    // reference's operation order: `sinThetaI2 = 1. - cosThetaI2` is a double subtraction rounded to float, `4 * eta2 * etak2` is
+    // (4 * eta2) * etak2, `0.5 * (Rp + Rs)` multiplies by 0.5 converted to Float
+    static Rgb fr_conductor(float cos_i, Rgb etat, Rgb k) {
+        cos_i = clampf(cos_i, -1, 1);
+        const float etai = 1.f;
+        const float cos2 = cos_i * cos_i;
+        const float sin2 = float(1. - double(cos2));
+        Rgb r;
+        for (int c = 0; c < 3; ++c) {
+            const float eta = etat.c[c] / etai, etak = k.c[c] / etai;
+            const float eta2 = eta * eta, etak2 = etak * etak;
+            const float t0 = eta2 - etak2 - sin2;
+            const float a2plusb2 = std::sqrt(t0 * t0 + 4.f * eta2 * etak2);
+            const float t1 = a2plusb2 + cos2;
+            const float a = std::sqrt(0.5f * (a2plusb2 + t0));
+            const float t2 = 2.f * cos_i * a;
+            const float Rs = (t1 - t2) / (t1 + t2);
+            const float t3 = cos2 * a2plusb2 + sin2 * sin2;
+            const float t4 = t2 * sin2;
+            const float Rp = Rs * (t3 - t4) / (t3 + t4);
+            r.c[c] = float(0.5) * (Rp + Rs);
+        }
+        return r;
+    }
     // TrowbridgeReitzDistribution, microfacet.cpp:155-163, 176-184
     static float tr_d(V3 wh, float ax, float ay) {
         float t2 = tan2_theta(wh);
@@ -1840,7 +1911,9 @@ struct Oracle {
         if (cos_i == 0 || cos_o == 0) return Rgb(0.);
         if (wh.x == 0 && wh.y == 0 && wh.z == 0) return Rgb(0.);
         wh = normalize(wh);
-        Rgb F(fr_dielectric(dot(wi, wh), b.micro_eta_i, b.micro_eta_t));
+        // FresnelConductor::Evaluate (reflection.cpp:118-120) for metal, FresnelDielectric::Evaluate otherwise
+        Rgb F = b.micro_conductor ? fr_conductor(std::abs(dot(wi, wh)), b.cond_eta, b.cond_k)
+                                  : Rgb(fr_dielectric(dot(wi, wh), b.micro_eta_i, b.micro_eta_t));
         return b.ks * tr_d(wh, b.alpha, b.alpha_y) * tr_g(wo, wi, b.alpha, b.alpha_y) * F / (4 * cos_i * cos_o);
     }
     static float micro_pdf(const Bsdf &b, V3 wo, V3 wi) {  // reflection.cpp:419-423
@@ -1907,6 +1980,29 @@ struct Oracle {
         return b.kd * InvPi * (b.on_a + b.on_b * max_cos * sin_alpha * tan_beta);
     }
     static float lambert_pdf(V3 wo, V3 wi) { return same_hemisphere(wo, wi) ? std::abs(wi.z) * InvPi : 0; }
+    // FresnelBlend::f (reflection.cpp:285-298) and SchlickFresnel (reflection.h:485-488), Rd = kd, Rs = ks
+    static Rgb blend_f(const Bsdf &b, V3 wo, V3 wi) {
+        auto pow5 = [](float v) { return (v * v) * (v * v) * v; };
+        const float c = 28.f / (23.f * Pi);
+        const float fi = 1 - pow5(1 - .5f * std::abs(wi.z)), fo = 1 - pow5(1 - .5f * std::abs(wo.z));
+        Rgb diffuse;
+        for (int k = 0; k < 3; ++k) diffuse.c[k] = c * b.kd.c[k] * (1.f - b.ks.c[k]) * fi * fo;
+        V3 wh = wi + wo;
+        if (wh.x == 0 && wh.y == 0 && wh.z == 0) return Rgb(0.f);
+        wh = normalize(wh);
+        const float s = tr_d(wh, b.alpha, b.alpha_y) / (4 * absdot(wi, wh) * std::max(std::abs(wi.z), std::abs(wo.z)));
+        const float p5 = pow5(1 - dot(wi, wh));
+        Rgb r;
+        for (int k = 0; k < 3; ++k) r.c[k] = diffuse.c[k] + s * (b.ks.c[k] + p5 * (1.f - b.ks.c[k]));
+        return r;
+    }
+    // FresnelBlend::Pdf, reflection.cpp:470-475
+    static float blend_pdf(const Bsdf &b, V3 wo, V3 wi) {
+        if (!same_hemisphere(wo, wi)) return 0;
+        V3 wh = normalize(wo + wi);
+        const float pdf_wh = tr_pdf(wo, wh, b.alpha, b.alpha_y);
+        return .5f * (std::abs(wi.z) * InvPi + pdf_wh / (4 * dot(wo, wh)));
+    }
 
     // BSDF::f, reflection.cpp:686-699 (all lobes are BSDF_REFLECTION, non-specular)
     static Rgb bsdf_f(const Bsdf &b, V3 woW, V3 wiW) {
@@ -1917,6 +2013,7 @@ struct Oracle {
         if (reflect) {
             if (b.has_lambert) f = f + diffuse_f(b, wo, wi);
             if (b.has_micro) f = f + micro_f(b, wo, wi);
+            if (b.has_blend) f = f + blend_f(b, wo, wi);
         } else if (b.has_mtrans) {  // `(!reflect && (bxdfs[i]->type & BSDF_TRANSMISSION))`
             f = f + mtrans_f(b, wo, wi);
         }
@@ -1941,6 +2038,10 @@ struct Oracle {
             ++matching;
             pdf += mtrans_pdf(b, wo, wi);
         }
+        if (b.has_blend) {
+            ++matching;
+            pdf += blend_pdf(b, wo, wi);
+        }
         return matching > 0 ? pdf / matching : 0.f;
     }
     // BSDF::Sample_f, reflection.cpp:719-784. Returns f; *pdf is left untouched
@@ -1962,6 +2063,7 @@ struct Oracle {
         if (pick < 0 && b.has_lambert && count-- == 0) pick = 0;
         if (pick < 0 && b.has_micro && count-- == 0) pick = 1;
         if (pick < 0 && b.has_mtrans && count-- == 0) pick = 5;   // rough glass: MicrofacetTransmission behind MicrofacetReflection (glass.cpp:74-90)
+        if (pick < 0 && b.has_blend && count-- == 0) pick = 6;    // substrate's FresnelBlend, its only lobe
         if (pick < 0 && b.has_spec && allow_specular && count-- == 0) pick = 2;
         if (pick < 0 && b.has_t1 && allow_specular && count-- == 0) pick = 4;
         float ur[2] = {std::min(u[0] * matching - comp, OneMinusEpsilon), u[1]};
@@ -1991,6 +2093,24 @@ struct Oracle {
             if (!refract(wo, wh, eta, &wi)) return Rgb(0);  // `return 0`, pdf stays 0
             *pdf = mtrans_pdf(b, wo, wi);
             f = mtrans_f(b, wo, wi);
+        } else if (pick == 6) {  // FresnelBlend::Sample_f, reflection.cpp:450-468
+            float ub[2] = {ur[0], ur[1]};
+            bool same = true;
+            if (ub[0] < .5) {
+                ub[0] = std::min(2 * ub[0], OneMinusEpsilon);
+                wi = cosine_sample_hemisphere(ub);
+                if (wo.z < 0) wi.z *= -1;
+            } else {
+                ub[0] = std::min(2 * (ub[0] - .5f), OneMinusEpsilon);
+                V3 wh = tr_sample_wh(wo, ub, b.alpha, b.alpha_y);
+                wi = -wo + 2 * dot(wo, wh) * wh;  // Reflect()
+                same = same_hemisphere(wo, wi);   // else `return Spectrum(0.f)`: pdf stays 0
+            }
+            if (same) {
+                *pdf = blend_pdf(b, wo, wi);
+                f = blend_f(b, wo, wi);
+            } else
+                f = Rgb(0.f);
         } else if (pick >= 3) {  // SpecularTransmission::Sample_f, reflection.cpp:154-170 (mode == Radiance)
             const float eta_a = 1.f, eta_b = pick == 3 ? 1.f : b.t1_eta;
             const bool entering = wo.z > 0;
@@ -2049,11 +2169,12 @@ struct Oracle {
             return Rgb(0);
         }
         *wiW = b.to_world(wi);
-        const bool specular = pick >= 2 && pick != 5;
+        const bool specular = pick >= 2 && pick <= 4;
         if (!specular && matching > 1) {  // a specular lobe's Pdf() is 0
             if (pick != 0 && b.has_lambert) *pdf += lambert_pdf(wo, wi);
             if (pick != 1 && b.has_micro) *pdf += micro_pdf(b, wo, wi);
             if (pick != 5 && b.has_mtrans) *pdf += mtrans_pdf(b, wo, wi);
+            if (pick != 6 && b.has_blend) *pdf += blend_pdf(b, wo, wi);
         }
         if (matching > 1) *pdf /= matching;
         if (!specular && matching > 1) {  // a specular lobe's f() is 0
@@ -2062,6 +2183,7 @@ struct Oracle {
             if (reflect) {
                 if (b.has_lambert) f = f + diffuse_f(b, wo, wi);
                 if (b.has_micro) f = f + micro_f(b, wo, wi);
+                if (b.has_blend) f = f + blend_f(b, wo, wi);
             } else if (b.has_mtrans) {
                 f = f + mtrans_f(b, wo, wi);
             }
@@ -3209,11 +3331,48 @@ struct FilmTile {
     std::vector<TilePixel> px;
 };
 
+// What the restatement covers, checked before any entry point reads the scene: anything else would be read through the wrong
+// arrays (a quadric index into the triangle data, a procedural texture as an empty image pyramid) instead of being refused.
+// Each check returns 0 or the ORACLE_UNSUPPORTED_* code of the first feature it does not restate (oracle.h).
+int check_texture(const iile_scene_desc &S, int tex) {
+    if (tex < 0 || tex >= S.n_textures) return 0;
+    const iile_texture &t = S.textures[tex];
+    if (t.mapping != IILE_MAP_UV) return ORACLE_UNSUPPORTED_MAPPING + t.mapping;
+    if (t.kind != IILE_TEX_IMAGE) return ORACLE_UNSUPPORTED_TEXTURE + t.kind;
+    return 0;
+}
+int check_material_type(const iile_scene_desc &S, int mat) {  // the BSDF probes, which look up no texture
+    if (mat < 0 || mat >= S.n_materials) return 0;
+    const int type = S.materials[mat].type;
+    return type < IILE_MAT_MATTE || type > IILE_MAT_SUBSTRATE ? ORACLE_UNSUPPORTED_MATERIAL + type : 0;
+}
+int check_material(const iile_scene_desc &S, int mat) {
+    if (int rc = check_material_type(S, mat)) return rc;
+    if (mat < 0 || mat >= S.n_materials) return 0;
+    const iile_material &m = S.materials[mat];
+    for (int tex : {m.kd_tex, m.ks_tex, m.kr_tex, m.kt_tex, m.bump_tex, m.rough_tex, m.sigma_tex, m.opacity_tex, m.rough_tex_v})
+        if (int rc = check_texture(S, tex)) return rc;
+    return 0;
+}
+int check_geometry(const iile_scene_desc &S) {
+    for (int i = 0; i < S.n_prims; ++i)
+        if (S.prim_flags[i] & IILE_PRIM_QUADRIC) return ORACLE_UNSUPPORTED_PRIM + IILE_PRIM_QUADRIC;
+    for (int i = 0; i < S.n_lights; ++i)
+        if (S.lights[i].type == IILE_LIGHT_AREA_QUADRIC) return ORACLE_UNSUPPORTED_LIGHT + S.lights[i].type;
+    return 0;
+}
+int check_scene(const iile_scene_desc *scene) {
+    if (!scene) return 0;
+    const iile_scene_desc &S = *scene;
+    if (int rc = check_geometry(S)) return rc;
+    for (int i = 0; i < S.n_materials; ++i)
+        if (int rc = check_material(S, i)) return rc;
+    for (int i = 0; i < S.n_textures; ++i)
+        if (int rc = check_texture(S, i)) return rc;
+    return 0;
+}
+
 }  // namespace
-
-extern "C" {
-
-}  // extern "C"
 
 // SamplerIntegrator::Render's tile loop (integrator.cpp:227-339); with `probe`: IISPTdIntegrator::RenderView
 // (iispt_d.cpp:388-470) — pixels outside the film's pixel bounds are skipped (:428-429) and the first hits' camera-space
@@ -3350,6 +3509,7 @@ int oracle_tile_owner(int tx, int ty, int nranks) { return iile_tile_owner(tx, t
 // ---- the IISPT runner's gather (iisptrenderrunner.cpp:248-596) -------------------------------------------------
 // hemi points of a task: find_intersection for each, then the aux ray the probe camera is placed on
 int oracle_iispt_hemi_points(const iile_scene_desc *scene, int trig_mode, const iile_iispt_task *task, uint8_t *valid, float *pos3, float *dir3) {
+    if (int rc = check_scene(scene)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
     const int nx = iile_iispt_grid_count(task->x0, task->x1, task->tilesize), ny = iile_iispt_grid_count(task->y0, task->y1, task->tilesize);
@@ -3378,6 +3538,7 @@ int oracle_iispt_hemi_points(const iile_scene_desc *scene, int trig_mode, const 
 // zeros where the runner records nothing
 int oracle_iispt_gather(const iile_scene_desc *scene, int trig_mode, const iile_iispt_task *task, const uint8_t *valid, const float *pos3,
                         const float *dir3, const float *nn_films, float *out_rgbw) {
+    if (int rc = check_scene(scene)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
     const int hemi = scene->probe.hemi_size;
@@ -3434,6 +3595,7 @@ int oracle_iispt_gather(const iile_scene_desc *scene, int trig_mode, const iile_
 
 int oracle_render(const iile_scene_desc *scene, int trig_mode, int n_threads, int k_begin, int k_end, int tile_rank,
                   int tile_nranks, float *film_xyzw, oracle_stats *stats) {
+    if (int rc = check_scene(scene)) return rc;
     return render_impl(scene, trig_mode, n_threads, k_begin, k_end, tile_rank, tile_nranks, film_xyzw, stats, nullptr, nullptr);
 }
 
@@ -3442,6 +3604,7 @@ int oracle_render(const iile_scene_desc *scene, int trig_mode, int n_threads, in
 // raster coordinates (the reference's ImageFilm stores row height - 1 - y, imagefilm.cpp:26-31, film.cpp:245-254).
 int oracle_render_probe(const iile_scene_desc *scene, int trig_mode, const float *pos3, const float *dir3, float *intensity_rgb,
                         float *normals_xyz, float *distance) {
+    if (int rc = check_scene(scene)) return rc;
     if (!scene || !pos3 || !dir3) return 1;
     const iile_probe_setup &pr = scene->probe;
     ProbeCam cam;
@@ -3576,8 +3739,9 @@ void oracle_camera_ray(const iile_scene_desc *scene, float pfx, float pfy, float
         d3[i] = r.d[i];
     }
 }
-void oracle_intersect(const iile_scene_desc *scene, int n, const float *o, const float *d, const float *tmax,
+int oracle_intersect(const iile_scene_desc *scene, int n, const float *o, const float *d, const float *tmax,
                       int32_t *prim, float *tb) {
+    if (int rc = check_geometry(*scene)) return rc;
     Counters c;
     Oracle orc(*scene, ORACLE_TRIG_PORTABLE, &c);
     for (int i = 0; i < n; ++i) {
@@ -3590,18 +3754,22 @@ void oracle_intersect(const iile_scene_desc *scene, int n, const float *o, const
         tb[4 * i + 2] = hit ? is.b1 : 0;
         tb[4 * i + 3] = hit ? is.b2 : 0;
     }
+    return 0;
 }
-void oracle_intersect_p(const iile_scene_desc *scene, int n, const float *o, const float *d, const float *tmax,
+int oracle_intersect_p(const iile_scene_desc *scene, int n, const float *o, const float *d, const float *tmax,
                         int32_t *hit) {
+    if (int rc = check_geometry(*scene)) return rc;
     Counters c;
     Oracle orc(*scene, ORACLE_TRIG_PORTABLE, &c);
     for (int i = 0; i < n; ++i) {
         Ray r{V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmax[i]};
         hit[i] = orc.intersect_p(r) ? 1 : 0;
     }
+    return 0;
 }
-void oracle_li(const iile_scene_desc *scene, int trig_mode, int n, const int32_t *px, const int32_t *py,
+int oracle_li(const iile_scene_desc *scene, int trig_mode, int n, const int32_t *px, const int32_t *py,
                const int32_t *k, float *L, int32_t *nrays) {
+    if (int rc = check_scene(scene)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
     for (int i = 0; i < n; ++i) {
@@ -3614,32 +3782,41 @@ void oracle_li(const iile_scene_desc *scene, int trig_mode, int n, const int32_t
             nrays[2 * i + 1] = int32_t(c.shadow_rays - s0);
         }
     }
+    return 0;
 }
 // the material's BSDF in the canonical frame ns = ng = +z, ss = +x (constant parameters: image textures are not looked up)
-static Oracle::Bsdf local_bsdf(const Oracle &orc, const iile_scene_desc *scene, int mat) {
+// (ng3: the geometric normal, +z when null: BSDF::f's reflect test and the recomputed f of a multi-lobe Sample_f read it)
+static Oracle::Bsdf local_bsdf(const Oracle &orc, const iile_scene_desc *scene, int mat, const float *ng3 = nullptr) {
     iile_material m = scene->materials[mat];
     m.kd_tex = m.ks_tex = m.kr_tex = m.kt_tex = m.bump_tex = m.rough_tex = m.sigma_tex = m.opacity_tex = -1;
     if (m.rough_tex_v >= 0) m.rough_tex_v = -1;
     Isect is;
-    is.sn = is.n = V3(0, 0, 1);
+    is.sn = V3(0, 0, 1);
+    is.n = ng3 ? V3(ng3[0], ng3[1], ng3[2]) : V3(0, 0, 1);
     is.sdpdu = V3(1, 0, 0);
     return orc.make_bsdf_of(m, is);
 }
-void oracle_bsdf_eval(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, const float *wi3,
-                      float *f3, float *pdf) {
+int oracle_bsdf_eval_ng(const iile_scene_desc *scene, int trig_mode, int mat, const float *ng3, const float *wo3, const float *wi3,
+                        float *f3, float *pdf) {
+    if (int rc = check_material_type(*scene, mat)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
-    Oracle::Bsdf b = local_bsdf(orc, scene, mat);
+    Oracle::Bsdf b = local_bsdf(orc, scene, mat, ng3);
     V3 wo(wo3[0], wo3[1], wo3[2]), wi(wi3[0], wi3[1], wi3[2]);
     Rgb f = Oracle::bsdf_f(b, wo, wi);
     for (int i = 0; i < 3; ++i) f3[i] = f.c[i];
     *pdf = Oracle::bsdf_pdf(b, wo, wi);
+    return 0;
 }
-void oracle_bsdf_sample(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, const float *u2,
-                        float *wi3, float *f3, float *pdf) {
+int oracle_bsdf_eval(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, const float *wi3, float *f3, float *pdf) {
+    return oracle_bsdf_eval_ng(scene, trig_mode, mat, nullptr, wo3, wi3, f3, pdf);
+}
+int oracle_bsdf_sample_ng(const iile_scene_desc *scene, int trig_mode, int mat, const float *ng3, const float *wo3, const float *u2,
+                          float *wi3, float *f3, float *pdf) {
+    if (int rc = check_material_type(*scene, mat)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
-    Oracle::Bsdf b = local_bsdf(orc, scene, mat);
+    Oracle::Bsdf b = local_bsdf(orc, scene, mat, ng3);
     V3 wo(wo3[0], wo3[1], wo3[2]), wi;
     float p = 0;
     Rgb f = orc.bsdf_sample_f(b, wo, &wi, u2, &p);
@@ -3648,9 +3825,15 @@ void oracle_bsdf_sample(const iile_scene_desc *scene, int trig_mode, int mat, co
         wi3[i] = wi[i];
     }
     *pdf = p;
+    return 0;
 }
-void oracle_bsdf_sample_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
+int oracle_bsdf_sample(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, const float *u2, float *wi3, float *f3,
+                       float *pdf) {
+    return oracle_bsdf_sample_ng(scene, trig_mode, mat, nullptr, wo3, u2, wi3, f3, pdf);
+}
+int oracle_bsdf_sample_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
                               const float *u2n, float *wi3n, float *pdfn) {
+    if (int rc = check_material_type(*scene, mat)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
     Oracle::Bsdf b = local_bsdf(orc, scene, mat);
@@ -3663,18 +3846,22 @@ void oracle_bsdf_sample_batch(const iile_scene_desc *scene, int trig_mode, int m
         for (int k = 0; k < 3; ++k) wi3n[3 * i + k] = wi[k];
         pdfn[i] = p;
     }
+    return 0;
 }
-void oracle_bsdf_pdf_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
+int oracle_bsdf_pdf_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
                            const float *wi3n, float *pdfn) {
+    if (int rc = check_material_type(*scene, mat)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
     Oracle::Bsdf b = local_bsdf(orc, scene, mat);
     V3 wo(wo3[0], wo3[1], wo3[2]);
     for (int i = 0; i < n; ++i)
         pdfn[i] = Oracle::bsdf_pdf(b, wo, V3(wi3n[3 * i], wi3n[3 * i + 1], wi3n[3 * i + 2]));
+    return 0;
 }
-void oracle_texture_eval(const iile_scene_desc *scene, int trig_mode, int tex, int n, const float *uv2, const float *duv4,
+int oracle_texture_eval(const iile_scene_desc *scene, int trig_mode, int tex, int n, const float *uv2, const float *duv4,
                          float *rgb3) {
+    if (int rc = check_texture(*scene, tex)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
     for (int i = 0; i < n; ++i) {
@@ -3688,8 +3875,10 @@ void oracle_texture_eval(const iile_scene_desc *scene, int trig_mode, int tex, i
         Rgb v = orc.tex_evaluate(tex, is);
         for (int k = 0; k < 3; ++k) rgb3[3 * i + k] = v.c[k];
     }
+    return 0;
 }
 int oracle_camera_hit_differentials(const iile_scene_desc *scene, int trig_mode, float pfx, float pfy, float *out6) {
+    if (int rc = check_scene(scene)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
     const float plens[2] = {0.5f, 0.5f};
@@ -3708,6 +3897,7 @@ int oracle_camera_hit_differentials(const iile_scene_desc *scene, int trig_mode,
 }
 // The closest hit's differential geometry as the direct pass reads it: out24 = {p, n, shading n, dpdu, dpdv, shading dndu, dndv, {prim, -, -}}
 int oracle_hit_geometry(const iile_scene_desc *scene, int trig_mode, const float *o3, const float *d3, float *out24) {
+    if (int rc = check_geometry(*scene)) return rc;
     Counters c;
     Oracle orc(*scene, trig_mode, &c);
     Ray ray{V3(o3[0], o3[1], o3[2]), V3(d3[0], d3[1], d3[2]), std::numeric_limits<float>::infinity()};
@@ -3843,8 +4033,9 @@ void oracle_sphere_solid_angle(const iile_scene_desc *scene, int sphere, const f
     *by_uniform_directions = hits / ((1.0 / (4 * 3.14159265358979323846)) * n_samples);
 }
 
-void oracle_light_solid_angle(const iile_scene_desc *scene, int light, const float *p3, int n_samples,
+int oracle_light_solid_angle(const iile_scene_desc *scene, int light, const float *p3, int n_samples,
                               double *by_sampling, double *by_uniform_directions) {
+    if (int rc = check_geometry(*scene)) return rc;
     Counters c;
     Oracle orc(*scene, ORACLE_TRIG_LIBM, &c);
     const iile_light &lt = scene->lights[light];
@@ -3870,6 +4061,7 @@ void oracle_light_solid_angle(const iile_scene_desc *scene, int light, const flo
     }
     *by_sampling = sa;
     *by_uniform_directions = hits / (double(n_samples) * (1.0 / (4 * 3.14159265358979323846)));
+    return 0;
 }
 
 int64_t oracle_check_next_float(int iters, uint64_t seed) {
@@ -3958,6 +4150,7 @@ extern "C" {
 // so GlassMaterial adds SpecularReflection + SpecularTransmission (glass.cpp:62-90) and Li recurses through both: a tree, walked here
 // by the recursion itself (round 3 assumed FresnelSpecular and rendered glass black; the device pass refuses glass).
 int oracle_iispt_direct(const iile_scene_desc *scene, int trig_mode, int n_passes, int first_pass, int n_threads, double *film_rgbw) {
+    if (int rc = check_scene(scene)) return rc;
     if (!scene || !film_rgbw || n_passes < 0) return 1;
     const iile_scene_desc &S = *scene;
     const iile_film_desc &F = S.film;

@@ -273,6 +273,24 @@ def boxroom_pbrt(xres=64, yres=64, spp=4, ico_levels=4, n_blobs=6, wall_n=24, se
         elif materials == "glass" and b % 2 == 1:  # closed refractive blobs, one of them tinted
             mat = 'Material "glass" "color Kr" [1 1 1] "color Kt" [%g %g %g] "float index" [%g]' % (
                 *((1, 1, 1) if b % 4 == 1 else rng.uniform(.7, 1, 3)), rng.uniform(1.3, 1.7))
+        elif materials == "metal":  # metal and substrate (metal.cpp, substrate.cpp); with `textures`, image-textured parameters and bump maps
+            k = b % 6
+            if k == 0:  # the default copper, one roughness
+                mat = 'Material "metal" "float roughness" [%g]' % rng.uniform(.02, .3)
+            elif k == 1:  # eta and k given, anisotropic
+                mat = 'Material "metal" "rgb eta" [%g %g %g] "rgb k" [%g %g %g] "float uroughness" [%g] "float vroughness" [%g]' % (
+                    *rng.uniform(.1, 1.7, 3), *rng.uniform(1.5, 9, 3), rng.uniform(.02, .4), rng.uniform(.02, .4))
+            elif k == 2:  # substrate, anisotropic
+                mat = 'Material "substrate" "rgb Kd" [%g %g %g] "rgb Ks" [%g %g %g] "float uroughness" [%g] "float vroughness" [%g]' % (
+                    *rng.uniform(.1, .8, 3), *rng.uniform(.02, .4, 3), rng.uniform(.02, .4), rng.uniform(.02, .4))
+            elif tex is None:  # without remapping
+                mat = ('Material "metal" "bool remaproughness" ["false"] "float uroughness" [%g] "float vroughness" [%g]',
+                       'Material "substrate" "bool remaproughness" ["false"] "float uroughness" [%g] "float vroughness" [%g]',
+                       'Material "metal" "float vroughness" [%g] "float roughness" [%g]')[k - 3] % tuple(rng.uniform(.05, .5, 2))
+            else:
+                mat = ('Material "substrate" "texture Kd" ["checker"] "texture Ks" ["noise-tint"] "texture uroughness" ["rough"] "float vroughness" [.2]',
+                       'Material "metal" "texture roughness" ["rough"] "float vroughness" [.1] "texture bumpmap" ["bumps"]',
+                       'Material "substrate" "texture Kd" ["stripes"] "rgb Ks" [.05 .05 .05] "texture bumpmap" ["bumps"]')[k - 3]
         elif tex is not None and b % 4 == 0:  # blobs have no uv: every triangle maps the unit half-square
             mat = 'Material "plastic" "texture Kd" ["noise"] "texture Ks" ["stripes"] "texture roughness" ["rough"]'
             rng.uniform(.02, .3)

@@ -28,6 +28,30 @@ class OracleStats(ctypes.Structure):
         return d
 
 
+# oracle.h ORACLE_UNSUPPORTED_*: a scene feature the restatement does not cover, refused before the scene is read
+_UNSUPPORTED = {1000: ("primitive", {32: "quadric (disk or cylinder)"}),
+                2000: ("light", {6: "area light on a quadric"}),
+                3000: ("material", {5: "metal", 6: "substrate"}),
+                4000: ("texture", {1: "scale", 2: "mix", 3: "checkerboard (2D)", 4: "checkerboard (3D)", 5: "uv", 6: "bilerp"}),
+                5000: ("texture mapping", {1: "spherical", 2: "cylindrical", 3: "planar"})}
+
+
+class OracleUnsupported(RuntimeError):
+    """The oracle refused a scene with a feature it does not restate; `feature` names it."""
+
+    def __init__(self, entry, code):
+        kind, names = _UNSUPPORTED[code // 1000 * 1000]
+        self.code, self.feature = code, f"{kind} {names.get(code % 1000, code % 1000)}"
+        super().__init__(f"{entry}: the oracle does not restate this scene's {self.feature}")
+
+
+def _check(entry, rc):
+    """Raises OracleUnsupported for an ORACLE_UNSUPPORTED_* return code; returns rc otherwise."""
+    if rc >= 1000 and rc // 1000 * 1000 in _UNSUPPORTED:
+        raise OracleUnsupported(entry, rc)
+    return rc
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -104,7 +128,7 @@ class Oracle:
         st = OracleStats()
         rc = self.lib.oracle_render(scene.desc, trig_mode, threads, k_begin, k_end, tile_rank, tile_nranks,
                                     film.ctypes.data, ctypes.byref(st))
-        assert rc == 0
+        assert _check("oracle_render", rc) == 0
         return film, st.as_dict()
 
     def iispt_hemi_points(self, scene, task, trig_mode=TRIG_PORTABLE):
@@ -114,7 +138,7 @@ class Oracle:
         dr = np.zeros((ny, nx, 3), np.float32)
         self.lib.oracle_iispt_hemi_points.argtypes = [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]
         n = self.lib.oracle_iispt_hemi_points(scene.desc, trig_mode, ctypes.byref(task), valid.ctypes.data, pos.ctypes.data, dr.ctypes.data)
-        assert n == nx * ny
+        assert _check("oracle_iispt_hemi_points", n) == nx * ny
         return valid, pos, dr
 
     def iispt_gather(self, scene, task, valid, pos, direction, nn_films, trig_mode=TRIG_PORTABLE):
@@ -123,7 +147,7 @@ class Oracle:
         self.lib.oracle_iispt_gather.argtypes = [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
         rc = self.lib.oracle_iispt_gather(scene.desc, trig_mode, ctypes.byref(task), valid.ctypes.data, pos.ctypes.data, direction.ctypes.data,
                                           nn.ctypes.data, out.ctypes.data)
-        assert rc == 0
+        assert _check("oracle_iispt_gather", rc) == 0
         return out
 
     def bvh_hlbvh(self, bounds6, max_prims_in_node=4):
@@ -153,7 +177,7 @@ class Oracle:
         f = self.lib.oracle_iispt_direct
         f.restype = ctypes.c_int
         f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        rc = f(scene.desc, trig_mode, int(n_passes), int(first_pass), int(threads), film.ctypes.data)
+        rc = _check("oracle_iispt_direct", f(scene.desc, trig_mode, int(n_passes), int(first_pass), int(threads), film.ctypes.data))
         if rc != 0:
             raise RuntimeError(f"oracle_iispt_direct: {rc}")
         return film
@@ -210,14 +234,15 @@ class Oracle:
         n = len(tmax)
         prim = np.empty(n, np.int32)
         tb = np.empty((n, 4), np.float32)
-        self.lib.oracle_intersect(scene.desc, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, prim.ctypes.data,
-                                  tb.ctypes.data)
+        _check("oracle_intersect", self.lib.oracle_intersect(scene.desc, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data,
+                                                             prim.ctypes.data, tb.ctypes.data))
         return prim, tb
 
     def light_solid_angle(self, scene, light, p, n_samples):
         p = _f32(p)
         a, b = ctypes.c_double(), ctypes.c_double()
-        self.lib.oracle_light_solid_angle(scene.desc, light, p.ctypes.data, n_samples, ctypes.byref(a), ctypes.byref(b))
+        _check("oracle_light_solid_angle",
+               self.lib.oracle_light_solid_angle(scene.desc, light, p.ctypes.data, n_samples, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
     def sphere_solid_angle(self, scene, sphere, p, n_samples):
@@ -243,7 +268,7 @@ class Oracle:
         o, d, tmax = _f32(o), _f32(d), _f32(tmax)
         n = len(tmax)
         hit = np.empty(n, np.int32)
-        self.lib.oracle_intersect_p(scene.desc, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, hit.ctypes.data)
+        _check("oracle_intersect_p", self.lib.oracle_intersect_p(scene.desc, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, hit.ctypes.data))
         return hit
 
     def li(self, scene, px, py, k, trig_mode=TRIG_PORTABLE):
@@ -251,39 +276,49 @@ class Oracle:
         n = len(px)
         L = np.empty((n, 3), np.float32)
         nr = np.empty((n, 2), np.int32)
-        self.lib.oracle_li(scene.desc, trig_mode, n, px.ctypes.data, py.ctypes.data, k.ctypes.data, L.ctypes.data,
-                           nr.ctypes.data)
+        _check("oracle_li", self.lib.oracle_li(scene.desc, trig_mode, n, px.ctypes.data, py.ctypes.data, k.ctypes.data, L.ctypes.data,
+                                               nr.ctypes.data))
         return L, nr
 
-    def bsdf_eval(self, scene, mat, wo, wi, trig_mode=TRIG_PORTABLE):
+    def bsdf_eval(self, scene, mat, wo, wi, trig_mode=TRIG_PORTABLE, ng=None):
+        """{f (3), pdf} per (wo, wi) in the frame ns = +z, ss = +x; ng: the geometric normal (default +z)."""
         wo, wi = _f32(wo), _f32(wi)
+        keep = _f32(ng) if ng is not None else None
+        ngp = keep.ctypes.data if keep is not None else None
         out = np.empty((len(wo), 4), np.float32)
+        f = self.lib.oracle_bsdf_eval_ng
+        f.argtypes = [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
         for i in range(len(wo)):
-            self.lib.oracle_bsdf_eval(scene.desc, trig_mode, mat, wo[i].ctypes.data, wi[i].ctypes.data,
-                                      out[i].ctypes.data, out[i, 3:].ctypes.data)
+            _check("oracle_bsdf_eval", f(scene.desc, trig_mode, mat, ngp, wo[i].ctypes.data, wi[i].ctypes.data, out[i].ctypes.data,
+                                         out[i, 3:].ctypes.data))
         return out
 
-    def bsdf_sample(self, scene, mat, wo, u, trig_mode=TRIG_PORTABLE):
+    def bsdf_sample(self, scene, mat, wo, u, trig_mode=TRIG_PORTABLE, ng=None):
+        """{wi (3), f (3), pdf} per (wo, u), as bsdf_eval."""
         wo, u = _f32(wo), _f32(u)
+        keep = _f32(ng) if ng is not None else None
+        ngp = keep.ctypes.data if keep is not None else None
         out = np.zeros((len(wo), 7), np.float32)
+        f = self.lib.oracle_bsdf_sample_ng
+        f.argtypes = [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
         for i in range(len(wo)):
-            self.lib.oracle_bsdf_sample(scene.desc, trig_mode, mat, wo[i].ctypes.data, u[i].ctypes.data,
-                                        out[i].ctypes.data, out[i, 3:].ctypes.data, out[i, 6:].ctypes.data)
+            _check("oracle_bsdf_sample", f(scene.desc, trig_mode, mat, ngp, wo[i].ctypes.data, u[i].ctypes.data, out[i].ctypes.data,
+                                           out[i, 3:].ctypes.data, out[i, 6:].ctypes.data))
         return out
 
     def bsdf_sample_batch(self, scene, mat, wo, u, trig_mode=TRIG_LIBM):
         wo, u = _f32(wo), _f32(u)
         n = len(u)
         wi, pdf = np.empty((n, 3), np.float32), np.empty(n, np.float32)
-        self.lib.oracle_bsdf_sample_batch(scene.desc, trig_mode, mat, wo.ctypes.data, n, u.ctypes.data, wi.ctypes.data,
-                                          pdf.ctypes.data)
+        _check("oracle_bsdf_sample_batch", self.lib.oracle_bsdf_sample_batch(scene.desc, trig_mode, mat, wo.ctypes.data, n, u.ctypes.data,
+                                                                             wi.ctypes.data, pdf.ctypes.data))
         return wi, pdf
 
     def bsdf_pdf_batch(self, scene, mat, wo, wi, trig_mode=TRIG_LIBM):
         wo, wi = _f32(wo), _f32(wi)
         pdf = np.empty(len(wi), np.float32)
-        self.lib.oracle_bsdf_pdf_batch(scene.desc, trig_mode, mat, wo.ctypes.data, len(wi), wi.ctypes.data,
-                                       pdf.ctypes.data)
+        _check("oracle_bsdf_pdf_batch", self.lib.oracle_bsdf_pdf_batch(scene.desc, trig_mode, mat, wo.ctypes.data, len(wi), wi.ctypes.data,
+                                                                       pdf.ctypes.data))
         return pdf
 
     def render_probe(self, scene, pos, direction, hemi=32, trig_mode=TRIG_PORTABLE):
@@ -292,14 +327,15 @@ class Oracle:
         inten, nrm, dist = np.zeros((hemi, hemi, 3), np.float32), np.zeros((hemi, hemi, 3), np.float32), np.zeros((hemi, hemi), np.float32)
         rc = self.lib.oracle_render_probe(scene.desc, trig_mode, pos.ctypes.data, direction.ctypes.data, inten.ctypes.data,
                                           nrm.ctypes.data, dist.ctypes.data)
-        if rc != 0:
+        if _check("oracle_render_probe", rc) != 0:
             raise RuntimeError(f"oracle_render_probe failed ({rc})")
         return inten, nrm, dist
 
     def texture_eval(self, scene, tex, uv, duv, trig_mode=TRIG_PORTABLE):
         uv, duv = _f32(uv), _f32(duv)
         out = np.empty((len(uv), 3), np.float32)
-        self.lib.oracle_texture_eval(scene.desc, trig_mode, tex, len(uv), uv.ctypes.data, duv.ctypes.data, out.ctypes.data)
+        _check("oracle_texture_eval",
+               self.lib.oracle_texture_eval(scene.desc, trig_mode, tex, len(uv), uv.ctypes.data, duv.ctypes.data, out.ctypes.data))
         return out
 
     def hit_geometry(self, scene, o, d, trig_mode=TRIG_LIBM):
@@ -307,13 +343,13 @@ class Oracle:
         o, d = _f32(o), _f32(d)
         out = np.zeros(24, np.float32)
         self.lib.oracle_hit_geometry.argtypes = [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]
-        if not self.lib.oracle_hit_geometry(scene.desc, trig_mode, o.ctypes.data, d.ctypes.data, out.ctypes.data):
+        if not _check("oracle_hit_geometry", self.lib.oracle_hit_geometry(scene.desc, trig_mode, o.ctypes.data, d.ctypes.data, out.ctypes.data)):
             return None
         return out[:21].reshape(7, 3)
 
     def camera_hit_differentials(self, scene, pfx, pfy, trig_mode=TRIG_PORTABLE):
         out = np.zeros(6, np.float32)
-        if not self.lib.oracle_camera_hit_differentials(scene.desc, trig_mode, pfx, pfy, out.ctypes.data):
+        if not _check("oracle_camera_hit_differentials", self.lib.oracle_camera_hit_differentials(scene.desc, trig_mode, pfx, pfy, out.ctypes.data)):
             return None
         return out
 
