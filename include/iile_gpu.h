@@ -28,7 +28,9 @@
  * Errors: the reference reports through Error()/LOG(FATAL) (src/core/error.h:54-55);
  * here every call returns 0 on success or a non-zero code, message in
  * iile_last_error(). There is NO CPU fallback: without a HIP device every
- * compute entry point fails with IILE_ERR_NO_DEVICE.
+ * compute entry point fails with IILE_ERR_NO_DEVICE. Descriptor errors are
+ * reported without a device, as for iile_bvh_build_hlbvh: iile_scene_create
+ * refuses a malformed or unsupported iile_scene_desc before any device call.
  * Threading: thread-compatible, not thread-safe (one scene per host thread).
  */
 #ifndef IILE_GPU_H

@@ -1045,18 +1045,11 @@ extern "C" int32_t iile_wide_ref_shift(void) { return kRefShift; }
 extern "C" int iile_bvh_pack_probe(int32_t n_nodes, const iile_bvh_node *nodes, int32_t n_interior, float *wide16, float *wide4_32,
                                    int32_t *nested) {
     if (n_nodes <= 0 || !nodes || !wide16 || !wide4_32 || !nested) return api_fail(IILE_ERR_ARG, "iile_bvh_pack_probe: bad argument");
-    // the checks iile_scene_create makes before it packs a tree it was handed: the kernel indexes by these fields, and the
-    // caller's buffers are sized by n_interior
+    // the node check of iile_scene_create without its bound on the leaf ranges: the kernel indexes by these fields, and
+    // the caller's buffers are sized by n_interior
     int counted = 0;
-    for (int i = 0; i < n_nodes; ++i) {
-        const iile_bvh_node &nd = nodes[i];
-        if (nd.nprims > 0) {
-            if (nd.offset < 0) return api_fail(IILE_ERR_ARG, "iile_bvh_pack_probe: bad leaf range");
-            continue;
-        }
-        if (i + 1 >= n_nodes || nd.offset <= i || nd.offset >= n_nodes) return api_fail(IILE_ERR_ARG, "iile_bvh_pack_probe: bad BVH child index");
-        ++counted;
-    }
+    const int bad = check_bvh_nodes(nodes, n_nodes, std::numeric_limits<int64_t>::max(), "iile_bvh_pack_probe: ", &counted);
+    if (bad) return bad;
     if (counted != n_interior) return api_fail(IILE_ERR_ARG, "iile_bvh_pack_probe: n_interior does not match the tree");
     int dev_count = 0;
     if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count <= 0)

@@ -126,6 +126,9 @@ struct LaunchCfg {
 
 // api.hip: records the message iile_last_error() returns, hands back `code`
 int api_fail(int code, const std::string &msg);
+// api.hip: the node check of a flattened tree a caller hands over (iile_scene_create, iile_bvh_pack_probe): leaf ranges in
+// [0, max_prims), an interior node's second child after it and inside the array; *n_interior = the interior nodes
+int check_bvh_nodes(const iile_bvh_node *nodes, int n_nodes, int64_t max_prims, const char *prefix, int *n_interior);
 // bvh_build.hip: two-wide (4 float4) and four-wide (8 float4) records per interior node of a flattened tree in HBM
 // (record index = rank of the node among the interior nodes in depth-first order, or d_remap[rank] when a record order is
 // given: a permutation of [0, n_interior)); *nested_out = every child box lies inside its parent's
