@@ -79,12 +79,13 @@ typedef struct iile_quadric {
     int32_t swaps_handedness;
 } iile_quadric;
 
+/* 7 is not a material type: a descriptor that names it is refused (IILE_ERR_UNSUPPORTED), and stays refused */
 enum { IILE_MAT_MATTE = 0, IILE_MAT_PLASTIC = 1, IILE_MAT_UBER = 2, IILE_MAT_MIRROR = 3, IILE_MAT_GLASS = 4, IILE_MAT_METAL = 5,
-       IILE_MAT_SUBSTRATE = 6 };
+       IILE_MAT_SUBSTRATE = 6, IILE_MAT_TRANSLUCENT = 8 };
 
-/* MatteMaterial / PlasticMaterial / UberMaterial / MirrorMaterial / GlassMaterial / MetalMaterial / SubstrateMaterial with constant
- * textures (src/materials/matte.cpp:45-62, plastic.cpp:45-70, uber.cpp:45-100, mirror.cpp:44-55,
- * glass.cpp:45-92, metal.cpp:58-79, substrate.cpp:45-79). Uber: its two SpecularTransmission lobes (the pass-through of opacity < 1 and Kt,
+/* MatteMaterial / PlasticMaterial / UberMaterial / MirrorMaterial / GlassMaterial / MetalMaterial / SubstrateMaterial /
+ * TranslucentMaterial with constant textures (src/materials/matte.cpp:45-62, plastic.cpp:45-70, uber.cpp:45-100, mirror.cpp:44-55,
+ * glass.cpp:45-92, metal.cpp:58-79, substrate.cpp:45-79, translucent.cpp:45-80). Uber: its two SpecularTransmission lobes (the pass-through of opacity < 1 and Kt,
  * uber.cpp:53-61, 94-99) are rendered by every entry point (the path and probe passes, the IISPT runner's stages, the direct pass).
  * Glass: smooth (uroughness = vroughness = 0: one FresnelSpecular lobe, as the path integrator gets it) or rough
  * (uroughness or vroughness != 0: MicrofacetReflection + MicrofacetTransmission, glass.cpp:66-90). */
@@ -129,7 +130,10 @@ typedef struct iile_material {
      * (default: the reference's copper, RGBSpectrum::FromSampled of CopperN / CopperK, metal.cpp:90-127); 0 for every other
      * material. Metal keeps "roughness" / "uroughness" in roughness / alpha / rough_tex and "vroughness" (or "roughness") in
      * roughness_v / alpha_v / rough_tex_v (-1: the constant): vRough = vRoughness ? vRoughness : roughness (metal.cpp:68-71).
-     * Substrate (substrate.cpp:45-79): FresnelBlend(Kd, Ks) over "uroughness" / "vroughness" in the same fields as metal */
+     * Substrate (substrate.cpp:45-79): FresnelBlend(Kd, Ks) over "uroughness" / "vroughness" in the same fields as metal.
+     * Translucent (translucent.cpp:45-98) adds no field: "Kd" is kd / kd_tex, "Ks" ks / ks_tex, "reflect" kr / kr_tex, "transmit"
+     * kt / kt_tex, the isotropic "roughness" roughness / alpha / rough_tex (alpha_v = alpha, rough_tex_v -2), "remaproughness"
+     * remap_roughness, "bumpmap" bump_tex, and eta is 1.5; opacity is 1 and cond_eta / cond_k are 0 */
     float cond_eta[3], cond_k[3];
 } iile_material;
 

@@ -118,6 +118,7 @@ class Material(ctypes.Structure):
 
 
 MAT_MATTE, MAT_PLASTIC, MAT_UBER, MAT_MIRROR, MAT_GLASS, MAT_METAL, MAT_SUBSTRATE = range(7)
+MAT_TRANSLUCENT = 8  # (7 is not a material type)
 QUADRIC_DISK, QUADRIC_CYLINDER = 0, 1
 PRIM_SPHERE, PRIM_FLIP, PRIM_QUADRIC = 1, 8, 32
 LIGHT_AREA_QUADRIC = 6

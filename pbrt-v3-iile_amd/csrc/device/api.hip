@@ -600,8 +600,8 @@ int check_scene_desc(const iile_scene_desc &d) {
         }
     }
     for (int i = 0; i < d.n_materials; ++i)
-        if (d.materials[i].type < IILE_MAT_MATTE || d.materials[i].type > IILE_MAT_SUBSTRATE)
-            return fail(IILE_ERR_UNSUPPORTED, "unsupported material type");
+        if ((d.materials[i].type < IILE_MAT_MATTE || d.materials[i].type > IILE_MAT_SUBSTRATE) && d.materials[i].type != IILE_MAT_TRANSLUCENT)
+            return fail(IILE_ERR_UNSUPPORTED, "unsupported material type");   // (7 among them)
     if (d.halton.n_dims > kMaxHaltonDims) return fail(IILE_ERR_UNSUPPORTED, "too many Halton dimensions");
     const int need_dims = 5 + 8 * d.integrator.max_depth + 1;
     if (d.halton.n_dims < need_dims) return fail(IILE_ERR_ARG, "Halton table covers too few dimensions for maxdepth");
@@ -691,8 +691,10 @@ void set_kernel_flags(const iile_scene_desc &d, DScene &S) {
         }
         for (int t : material_textures(device_material(m, d.n_textures)))
             if (t >= 0) S.textured_materials = 1;
-        if (m.type != IILE_MAT_MATTE && m.type != IILE_MAT_PLASTIC && m.type != IILE_MAT_METAL && m.type != IILE_MAT_SUBSTRATE)
-            S.has_specular = 1;   // (metal and substrate: one glossy reflection lobe each, metal.cpp:79, substrate.cpp:62)
+        if (m.type != IILE_MAT_MATTE && m.type != IILE_MAT_PLASTIC && m.type != IILE_MAT_METAL && m.type != IILE_MAT_SUBSTRATE &&
+            m.type != IILE_MAT_TRANSLUCENT)
+            S.has_specular = 1;   // (metal and substrate: one glossy reflection lobe each, metal.cpp:79, substrate.cpp:62; translucent:
+                                  //  diffuse and glossy lobes only, translucent.cpp:62-78)
         if ((m.type != IILE_MAT_MATTE && m.type != IILE_MAT_PLASTIC) || (m.type == IILE_MAT_MATTE && m.sigma != 0))
             S.extended_features = 1;
     }
@@ -1234,7 +1236,7 @@ static_assert(kQuadricDisk == IILE_QUADRIC_DISK && kQuadricCylinder == IILE_QUAD
               "quadric kind codes");
 static_assert(kMatMatte == IILE_MAT_MATTE && kMatPlastic == IILE_MAT_PLASTIC && kMatUber == IILE_MAT_UBER &&
                   kMatMirror == IILE_MAT_MIRROR && kMatGlass == IILE_MAT_GLASS && kMatMetal == IILE_MAT_METAL &&
-                  kMatSubstrate == IILE_MAT_SUBSTRATE,
+                  kMatSubstrate == IILE_MAT_SUBSTRATE && kMatTranslucent == IILE_MAT_TRANSLUCENT,
               "material type codes");
 int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
     if (!d || !out) return fail(IILE_ERR_ARG, "iile_scene_create: null argument");

@@ -1448,7 +1448,7 @@ struct Bsdf {
     // rough glass (glass.cpp:66-90): MicrofacetReflection(kr -> ks, FresnelDielectric(1, eta)) is the microfacet lobe;
     // MicrofacetTransmission(kt, distrib, 1, eta, Radiance) — glossy, not specular
     bool has_mtrans;
-    int n_lobes;  // nBxDFs; BxDF order: [pass-through], Lambertian, microfacet, specular reflection, [uber's Kt lobe]
+    int n_lobes;  // nBxDFs; BxDF order: [pass-through], Lambertian, [Lambertian transmission], microfacet, specular reflection, [uber's Kt lobe]
     float on_a, on_b;  // Oren-Nayar constants of the diffuse lobe (oren_nayar set)
     bool oren_nayar;
     int mtype;    // kMat*: selects the Fresnel terms (plastic 1.5/1; uber 1/eta; mirror none; metal FresnelConductor(1, kr, kt))
@@ -1458,9 +1458,13 @@ struct Bsdf {
     // held in kr and kt (a metal has no specular lobe that would read them: has_spec is false)
     // substrate (substrate.cpp:45-66): FresnelBlend(Rd = kd, Rs = ks, distrib) — glossy reflection, the only lobe of its BSDF
     bool has_blend;
+    // translucent (translucent.cpp:45-80): LambertianReflection(r kd) is the Lambertian lobe; LambertianTransmission(t kd), its T held
+    // in kr (translucent has no specular lobe that would read it), comes next; MicrofacetReflection(r ks, FresnelDielectric(1, 1.5)) is
+    // the microfacet lobe and MicrofacetTransmission(t ks, distrib, 1, 1.5) rough glass's
+    bool has_ltrans;
 };
 DEV int n_nonspec(const Bsdf &b) {
-    return (b.has_lambert ? 1 : 0) + (b.has_micro ? 1 : 0) + (b.has_mtrans ? 1 : 0) + (b.has_blend ? 1 : 0);
+    return (b.has_lambert ? 1 : 0) + (b.has_ltrans ? 1 : 0) + (b.has_micro ? 1 : 0) + (b.has_mtrans ? 1 : 0) + (b.has_blend ? 1 : 0);
 }
 DEV F3 to_local(const Bsdf &b, F3 v) { return F3{dot(v, b.ss), dot(v, b.ts), dot(v, b.ns)}; }
 DEV F3 to_world(const Bsdf &b, F3 v) {
@@ -1864,8 +1868,8 @@ DEV DMaterial textured_material(const DScene &S, const DMaterial &m, const Isect
     return r;
 }
 
-// Matte / Plastic / Uber / Mirror / Glass / Metal / Substrate ComputeScatteringFunctions (matte.cpp:45-62, plastic.cpp:45-70,
-// uber.cpp:45-100, mirror.cpp:44-55, glass.cpp:45-92, metal.cpp:58-79, substrate.cpp:45-66)
+// Matte / Plastic / Uber / Mirror / Glass / Metal / Substrate / Translucent ComputeScatteringFunctions (matte.cpp:45-62,
+// plastic.cpp:45-70, uber.cpp:45-100, mirror.cpp:44-55, glass.cpp:45-92, metal.cpp:58-79, substrate.cpp:45-66, translucent.cpp:45-80)
 // EXT = false: the scene has matte and plastic only (checked at upload); the specular lobes then fold away
 template <bool EXT = true>
 DEV Bsdf make_bsdf(const DMaterial &m, const Isect &is) {
@@ -1953,6 +1957,23 @@ DEV Bsdf make_bsdf(const DMaterial &m, const Isect &is) {
         b.ks = F3{clampf(m_ks.x, 0, IILE_INF), clampf(m_ks.y, 0, IILE_INF), clampf(m_ks.z, 0, IILE_INF)};
         b.has_blend = !(is_black(b.kd) && is_black(b.ks));
         if (b.has_blend) ++b.n_lobes;
+    }
+    b.has_ltrans = false;
+    if (EXT && m_type == kMatTranslucent) {  // translucent.cpp:51-78: r = reflect.Clamp(), t = transmit.Clamp(); no lobe when both are black
+        const F3 r = F3{clampf(m.kr[0], 0, IILE_INF), clampf(m.kr[1], 0, IILE_INF), clampf(m.kr[2], 0, IILE_INF)};
+        const F3 t = F3{clampf(m.kt[0], 0, IILE_INF), clampf(m.kt[1], 0, IILE_INF), clampf(m.kt[2], 0, IILE_INF)};
+        const F3 kd = b.kd;   // Kd.Clamp()
+        const F3 ks = F3{clampf(m_ks.x, 0, IILE_INF), clampf(m_ks.y, 0, IILE_INF), clampf(m_ks.z, 0, IILE_INF)};
+        const bool r_on = !is_black(r), t_on = !is_black(t);
+        b.kd = r * kd;   // LambertianReflection
+        b.kr = t * kd;   // LambertianTransmission
+        b.ks = r * ks;   // MicrofacetReflection
+        b.kt = t * ks;   // MicrofacetTransmission
+        b.has_lambert = r_on && !is_black(kd);
+        b.has_ltrans = t_on && !is_black(kd);
+        b.has_micro = r_on && !is_black(ks);
+        b.has_mtrans = t_on && !is_black(ks);
+        b.n_lobes = (b.has_lambert ? 1 : 0) + (b.has_ltrans ? 1 : 0) + (b.has_micro ? 1 : 0) + (b.has_mtrans ? 1 : 0);
     }
     return b;
 }
@@ -2084,7 +2105,7 @@ DEV F3 tr_sample_wh(F3 wo, float u0, float u1, float ax, float ay) {
     if (flip) wh = -wh;
     return wh;
 }
-// MicrofacetReflection::f, reflection.cpp:226-236, with FresnelDielectric(1.5, 1) (plastic) or (1, e) (uber, glass), or
+// MicrofacetReflection::f, reflection.cpp:226-236, with FresnelDielectric(1.5, 1) (plastic) or (1, e) (uber, glass, translucent), or
 // FresnelConductor(1, eta, k) (metal: its Evaluate takes |cos|, reflection.cpp:118-120)
 DEV F3 micro_f(const Bsdf &b, F3 wo, F3 wi) {
     float cos_o = fabsf(wo.z), cos_i = fabsf(wi.z);
@@ -2096,7 +2117,8 @@ DEV F3 micro_f(const Bsdf &b, F3 wo, F3 wi) {
     if (b.mtype == kMatMetal) {
         F = fr_conductor(fabsf(dot(wi, wh)), b.kr, b.kt);
     } else {
-        float Fr = (b.mtype == kMatUber || b.mtype == kMatGlass) ? fr_dielectric(dot(wi, wh), 1.f, b.eta) : fr_dielectric(dot(wi, wh), 1.5f, 1.f);
+        float Fr = (b.mtype == kMatUber || b.mtype == kMatGlass || b.mtype == kMatTranslucent) ? fr_dielectric(dot(wi, wh), 1.f, b.eta)
+                                                                                              : fr_dielectric(dot(wi, wh), 1.5f, 1.f);
         F = F3{Fr, Fr, Fr};
     }
     return sdiv(b.ks * tr_d(wh, b.alpha, b.alpha_y) * tr_g(wo, wi, b.alpha, b.alpha_y) * F, 4 * cos_i * cos_o);
@@ -2147,6 +2169,10 @@ DEV F3 diffuse_f(const Bsdf &b, F3 wo, F3 wi) {
     return b.kd * kInvPi * (b.on_a + b.on_b * max_cos * sin_alpha * tan_beta);
 }
 DEV float lambert_pdf(F3 wo, F3 wi) { return same_hemisphere(wo, wi) ? fabsf(wi.z) * kInvPi : 0; }
+// LambertianTransmission::f / Pdf, reflection.cpp:187-190, 401-403: T / pi with no hemisphere test of its own (BSDF::f asks for a
+// transmission lobe only where wi and wo lie on opposite sides of ng); T is held in kr
+DEV F3 ltrans_f(const Bsdf &b) { return b.kr * kInvPi; }
+DEV float ltrans_pdf(F3 wo, F3 wi) { return !same_hemisphere(wo, wi) ? fabsf(wi.z) * kInvPi : 0; }
 // Refract, reflection.h:96-108
 DEV bool refract_dir(F3 wi, F3 n, float eta, F3 *wt) {
     const float cos_i = dot(n, wi);
@@ -2191,13 +2217,20 @@ DEV F3 lobes_f(const Bsdf &b, F3 wo, F3 wi) {
     if (b.has_blend) f = f + blend_f(b, wo, wi);
     return f;
 }
+// the BSDF_TRANSMISSION lobes that are not specular, summed in BxDF order: `(!reflect && (bxdfs[i]->type & BSDF_TRANSMISSION))`
+DEV F3 trans_lobes_f(const Bsdf &b, F3 wo, F3 wi) {
+    F3 f = F3{0, 0, 0};
+    if (b.has_ltrans) f = f + ltrans_f(b);
+    if (b.has_mtrans) f = f + mtrans_f(b, wo, wi);
+    return f;
+}
 // BSDF::f, reflection.cpp:686-699
 DEV F3 bsdf_f(const Bsdf &b, F3 woW, F3 wiW) {
     F3 wi = to_local(b, wiW), wo = to_local(b, woW);
     if (wo.z == 0) return F3{0, 0, 0};
     bool reflect = dot(wiW, b.ng) * dot(woW, b.ng) > 0;
     if (reflect) return lobes_f(b, wo, wi);
-    return b.has_mtrans ? F3{0, 0, 0} + mtrans_f(b, wo, wi) : F3{0, 0, 0};   // `(!reflect && (bxdfs[i]->type & BSDF_TRANSMISSION))`
+    return trans_lobes_f(b, wo, wi);
 }
 // BSDF::Pdf, reflection.cpp:786-801
 DEV float bsdf_pdf(const Bsdf &b, F3 woW, F3 wiW) {
@@ -2206,6 +2239,7 @@ DEV float bsdf_pdf(const Bsdf &b, F3 woW, F3 wiW) {
     if (wo.z == 0) return 0.f;
     float pdf = 0.f;
     if (b.has_lambert) pdf += lambert_pdf(wo, wi);
+    if (b.has_ltrans) pdf += ltrans_pdf(wo, wi);
     if (b.has_micro) pdf += micro_pdf(b, wo, wi);
     if (b.has_mtrans) pdf += mtrans_pdf(b, wo, wi);
     if (b.has_blend) pdf += blend_pdf(b, wo, wi);
@@ -2227,12 +2261,14 @@ DEV F3 bsdf_sample_f(const Bsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *
     int comp = int(floorf(u0 * matching));
     if (comp > matching - 1) comp = matching - 1;
     // the comp-th present lobe in BxDF order: [3 uber's pass-through], 0 Lambertian, 1 microfacet, 2 specular reflection, [4 uber's Kt lobe]
-    // (6: substrate's FresnelBlend, the one lobe of its BSDF)
+    // (6: substrate's FresnelBlend, the one lobe of its BSDF; 7: translucent's LambertianTransmission, right behind its Lambertian)
     int pick, count = comp;
     if (allow_specular && b.has_t0 && count-- == 0)
         pick = 3;
     else if (b.has_lambert && count-- == 0)
         pick = 0;
+    else if (b.has_ltrans && count-- == 0)
+        pick = 7;
     else if (b.has_micro && count-- == 0)
         pick = 1;
     else if (b.has_mtrans && count-- == 0)
@@ -2256,6 +2292,11 @@ DEV F3 bsdf_sample_f(const Bsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *
         if (wo.z < 0) wi.z *= -1;
         *pdf = lambert_pdf(wo, wi);
         f = diffuse_f(b, wo, wi);
+    } else if (pick == 7) {  // LambertianTransmission::Sample_f, reflection.cpp:391-398: the hemisphere opposite wo
+        wi = cosine_sample_hemisphere(ur0, u1);
+        if (wo.z > 0) wi.z *= -1;
+        *pdf = ltrans_pdf(wo, wi);
+        f = ltrans_f(b);
     } else if (pick == 1) {  // MicrofacetReflection::Sample_f, reflection.cpp:405-417
         F3 wh = tr_sample_wh(wo, ur0, u1, b.alpha, b.alpha_y);
         wi = -wo + 2 * dot(wo, wh) * wh;
@@ -2345,16 +2386,17 @@ DEV F3 bsdf_sample_f(const Bsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *
         return F3{0, 0, 0};
     }
     *wiW = to_world(b, wi);
-    const bool glossy = pick < 2 || pick == 5 || pick == 6;
+    const bool glossy = pick < 2 || pick == 5 || pick == 6 || pick == 7;
     if (glossy && matching > 1) {  // a specular lobe's Pdf() and f() are 0
         if (pick != 0 && b.has_lambert) *pdf += lambert_pdf(wo, wi);
+        if (pick != 7 && b.has_ltrans) *pdf += ltrans_pdf(wo, wi);
         if (pick != 1 && b.has_micro) *pdf += micro_pdf(b, wo, wi);
         if (pick != 5 && b.has_mtrans) *pdf += mtrans_pdf(b, wo, wi);
     }
     if (matching > 1) *pdf /= matching;
     if (glossy && matching > 1) {
         bool reflect = dot(*wiW, b.ng) * dot(woW, b.ng) > 0;
-        f = reflect ? lobes_f(b, wo, wi) : (b.has_mtrans ? F3{0, 0, 0} + mtrans_f(b, wo, wi) : F3{0, 0, 0});
+        f = reflect ? lobes_f(b, wo, wi) : trans_lobes_f(b, wo, wi);
     }
     return f;
 }

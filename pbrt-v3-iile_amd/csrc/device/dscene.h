@@ -33,7 +33,8 @@ struct DQuadric {
     float radius, inner_radius, height, zmin, zmax, phi_max;
     int reverse_orientation, swaps_handedness;
 };
-enum { kMatMatte = 0, kMatPlastic = 1, kMatUber = 2, kMatMirror = 3, kMatGlass = 4, kMatMetal = 5, kMatSubstrate = 6 };  // = IILE_MAT_* (checked in api.hip)
+enum { kMatMatte = 0, kMatPlastic = 1, kMatUber = 2, kMatMirror = 3, kMatGlass = 4, kMatMetal = 5, kMatSubstrate = 6,
+       kMatTranslucent = 8 };  // = IILE_MAT_* (checked in api.hip)
 // (16-byte aligned, and the fields every hit reads first: (type, kd) and (ks, alpha) are one float4 each, see make_bsdf)
 struct alignas(16) DMaterial {
     int type;

@@ -869,7 +869,8 @@ class Loader {
     // replaces references to named textures among a material's parameters by their values
     // (an image texture stays a reference: `image_of` gets parameter name -> texture index, and the
     // parameter a placeholder colour that the material's constant-value checks see as non-black)
-    bool resolve_textures(const ParamSet &in, ParamSet *out, std::map<std::string, int> *image_of) {
+    // (translucent: "reflect" and "transmit" take spectrum textures as Kd .. Kt do)
+    bool resolve_textures(const ParamSet &in, ParamSet *out, std::map<std::string, int> *image_of, bool translucent = false) {
         *out = in;
         for (Param &p : out->params) {
             if (p.type != "texture") continue;
@@ -884,8 +885,10 @@ class Loader {
                 continue;
             }
             if (it->second.image >= 0) {
-                if (it->second.is_float || (p.name != "Kd" && p.name != "Ks" && p.name != "Kr" && p.name != "Kt" && p.name != "opacity"))
-                    return fail("image texture \"" + p.strs[0] + "\" on parameter \"" + p.name + "\" is not supported (Kd, Ks, Kr, Kt, opacity)");
+                const bool rt = translucent && (p.name == "reflect" || p.name == "transmit");
+                if (it->second.is_float || (p.name != "Kd" && p.name != "Ks" && p.name != "Kr" && p.name != "Kt" && p.name != "opacity" && !rt))
+                    return fail("image texture \"" + p.strs[0] + "\" on parameter \"" + p.name + "\" is not supported (Kd, Ks, Kr, Kt, opacity" +
+                                (translucent ? ", reflect, transmit)" : ")"));
                 (*image_of)[p.name] = it->second.image;
                 p.strs.clear();
                 p.type = "color";  // the constant the image's value is multiplied with at the hit (1 unless "scale"d)
@@ -932,9 +935,18 @@ class Loader {
                 }
             }
         }
+        if (name == "translucent")  // its four spectra: rgb, color or a texture; what else pbrt-v3 takes is refused by name
+            for (const char *param : {"Kd", "Ks", "reflect", "transmit"}) {
+                const Param *p = ps_in.find(param);
+                if (p && (p->type == "spectrum" || p->type == "blackbody")) {
+                    fail(std::string("Material \"translucent\": parameter \"") + param + "\" given as \"" + p->type +
+                         "\" is not supported (rgb, color or a texture)");
+                    return -1;
+                }
+            }
         ParamSet ps;
         std::map<std::string, int> image_of;
-        if (!resolve_textures(ps_in, &ps, &image_of)) return -1;
+        if (!resolve_textures(ps_in, &ps, &image_of, name == "translucent")) return -1;
         iile_material m;
         std::memset(&m, 0, sizeof(m));
         m.kd_tex = m.ks_tex = m.kr_tex = m.kt_tex = m.bump_tex = m.rough_tex = m.sigma_tex = m.opacity_tex = -1;
@@ -1042,14 +1054,30 @@ class Loader {
             m.remap_roughness = ps.one_bool("remaproughness", true) ? 1 : 0;
             m.alpha = m.remap_roughness ? roughness_to_alpha(m.roughness) : m.roughness;
             m.alpha_v = m.remap_roughness ? roughness_to_alpha(m.roughness_v) : m.roughness_v;
+        } else if (name == "translucent") {  // CreateTranslucentMaterial, translucent.cpp:82-98
+            m.type = IILE_MAT_TRANSLUCENT;
+            float kd[3] = {.25f, .25f, .25f}, ks[3] = {.25f, .25f, .25f}, r[3] = {.5f, .5f, .5f}, t[3] = {.5f, .5f, .5f};
+            ps.rgb("Kd", kd);
+            ps.rgb("Ks", ks);
+            ps.rgb("reflect", r);
+            ps.rgb("transmit", t);
+            for (int i = 0; i < 3; ++i) m.kd[i] = kd[i], m.ks[i] = ks[i], m.kr[i] = r[i], m.kt[i] = t[i];
+            m.eta = 1.5f;   // translucent.cpp:50
+            m.roughness = m.roughness_v = ps.one_float("roughness", .1f);   // TrowbridgeReitzDistribution(rough, rough)
+            m.remap_roughness = ps.one_bool("remaproughness", true) ? 1 : 0;
+            // evaluated per hit in the reference (translucent.cpp:68-70); a per-material constant, so evaluated once here, as for plastic
+            m.alpha = m.alpha_v = m.remap_roughness ? roughness_to_alpha(m.roughness) : m.roughness;
         } else {
-            fail("Material \"" + name + "\" is not supported (matte, plastic, uber, mirror, glass, metal, substrate)");
+            fail("Material \"" + name + "\" is not supported (matte, plastic, uber, mirror, glass, metal, substrate, translucent)");
             return -1;
         }
         // which parameters each material looks up (an image given for one it does not have is ignored, as a
         // constant would be)
-        if (m.type == IILE_MAT_MATTE || m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER || m.type == IILE_MAT_SUBSTRATE) m.kd_tex = image("Kd");
-        if (m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER || m.type == IILE_MAT_SUBSTRATE) m.ks_tex = image("Ks");
+        if (m.type == IILE_MAT_MATTE || m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER || m.type == IILE_MAT_SUBSTRATE ||
+            m.type == IILE_MAT_TRANSLUCENT)
+            m.kd_tex = image("Kd");
+        if (m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER || m.type == IILE_MAT_SUBSTRATE || m.type == IILE_MAT_TRANSLUCENT) m.ks_tex = image("Ks");
+        if (m.type == IILE_MAT_TRANSLUCENT) m.kr_tex = image("reflect"), m.kt_tex = image("transmit");
         if (m.type == IILE_MAT_UBER || m.type == IILE_MAT_MIRROR || m.type == IILE_MAT_GLASS) m.kr_tex = image("Kr");
         if (m.type == IILE_MAT_GLASS || m.type == IILE_MAT_UBER) m.kt_tex = image("Kt");
         if (m.type == IILE_MAT_UBER) m.opacity_tex = image("opacity");   // GetSpectrumTexture("opacity", 1.f), uber.cpp:117
@@ -1066,10 +1094,11 @@ class Loader {
             const Param *rp = ps.find("roughness"), *up = ps.find("uroughness"), *vp = ps.find("vroughness");
             const bool r_img = rp && rp->type == "roughimage", u_img = up && up->type == "roughimage", v_img = vp && vp->type == "roughimage";
             const bool uv_mat = m.type == IILE_MAT_UBER || m.type == IILE_MAT_METAL || m.type == IILE_MAT_SUBSTRATE;
-            if ((r_img && m.type != IILE_MAT_PLASTIC && m.type != IILE_MAT_UBER && m.type != IILE_MAT_METAL && m.type != IILE_MAT_SUBSTRATE) ||
+            if ((r_img && m.type != IILE_MAT_PLASTIC && m.type != IILE_MAT_UBER && m.type != IILE_MAT_METAL && m.type != IILE_MAT_SUBSTRATE &&
+                 m.type != IILE_MAT_TRANSLUCENT) ||
                 ((u_img || v_img) && !uv_mat)) {
-                fail("roughness: a float \"imagemap\" texture is supported on plastic (\"roughness\"), uber and metal (\"roughness\", "
-                     "\"uroughness\", \"vroughness\") and substrate (\"uroughness\", \"vroughness\") only");
+                fail("roughness: a float \"imagemap\" texture is supported on plastic and translucent (\"roughness\"), uber and metal "
+                     "(\"roughness\", \"uroughness\", \"vroughness\") and substrate (\"uroughness\", \"vroughness\") only");
                 return -1;
             }
             if (m.type == IILE_MAT_METAL) {  // metal.cpp:68-71: each of u and v is its own parameter if given, else "roughness"
@@ -1085,7 +1114,7 @@ class Loader {
         }
         if (const Param *bp = ps.find("bumpmap")) {  // GetFloatTextureOrNull("bumpmap") of every material's Create*
             if (bp->type != "bumpimage" || m.type == IILE_MAT_GLASS) {
-                fail("bumpmap: only a float \"imagemap\" texture on matte / plastic / uber / mirror / metal / substrate is supported");
+                fail("bumpmap: only a float \"imagemap\" texture on matte / plastic / uber / mirror / metal / substrate / translucent is supported");
                 return -1;
             }
             m.bump_tex = image("bumpmap");
