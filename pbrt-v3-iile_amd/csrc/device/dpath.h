@@ -2690,4 +2690,172 @@ DEV float power_heuristic(float fpdf, float gpdf) {  // sampling.h:169-172 with 
     return (f * f) / (f * f + g * g);
 }
 
+// DiffuseAreaLight::L (lights/diffuse.h:56-58)
+DEV F3 area_light_L(const DLight &lt, F3 n, F3 w) {
+    return (lt.two_sided || dot(n, w) > 0) ? F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]} : F3{0, 0, 0};
+}
+// Sample_Li of a delta light at p: PointLight (lights/point.cpp:43-52), SpotLight with its Falloff (spot.cpp:53-76),
+// DistantLight (distant.cpp:50-61). The pdf is 1; *target is the light-side end of the shadow ray.
+DEV F3 delta_light_li(const DLight &lt, F3 p, F3 *wi, F3 *target) {
+    const F3 pos = F3{lt.pos[0], lt.pos[1], lt.pos[2]};
+    const F3 I = F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]};
+    if (lt.type == kLightDistant) {
+        *wi = pos;                                  // wLight
+        *target = p + pos * (2 * lt.world_radius);  // pOutside
+        return I;
+    }
+    *wi = normalize(pos - p);
+    *target = pos;  // pLight
+    if (lt.type != kLightSpot) return sdiv(I, length_sq(pos - p));
+    const F3 w = -*wi;
+    const F3 wl = normalize(F3{lt.w2l[0] * w.x + lt.w2l[1] * w.y + lt.w2l[2] * w.z,
+                               lt.w2l[3] * w.x + lt.w2l[4] * w.y + lt.w2l[5] * w.z,
+                               lt.w2l[6] * w.x + lt.w2l[7] * w.y + lt.w2l[8] * w.z});
+    const float cos_theta = wl.z;
+    float falloff;
+    if (cos_theta < lt.cos_total_width)
+        falloff = 0;
+    else if (cos_theta >= lt.cos_falloff_start)
+        falloff = 1;
+    else {
+        const float delta = (cos_theta - lt.cos_total_width) / (lt.cos_falloff_start - lt.cos_total_width);
+        falloff = (delta * delta) * (delta * delta);
+    }
+    return sdiv(I * falloff, length_sq(pos - p));
+}
+
+// One EstimateDirect call (integrator.cpp:108-215) as a REQUEST: the shadow ray (so, sd) of the light-sampling half with what it
+// adds if unoccluded (A), the closest-hit ray (mo, md) of the BSDF-sampling half with what it adds if it ends on the sampled
+// light (Bc). Returns NEE_HAS_SHADOW | NEE_HAS_MIS; an output is written only where its flag is set.
+// The wavefront kernels turn the request into an NEE record (k_mis / k_mis_lit / k_shadow resolve it), the per-pixel pass for
+// glass scenes (k_direct_tree) traces the two rays on the spot. ul0, ul1: uLight; us0, us1: uScattering.
+// lsp: the light's sphere where the caller has it at hand, else nullptr (the scene's entry is then read where a sphere light
+// needs it). EXT = false: the plain build, whose one light is an emitting sphere, *lsp (both wave-uniform, see uniform_entry).
+// COUNT: the instrumented build, which traces every MIS ray (no can_reach skip) and counts Shape::Pdf's Triangle::Intersect
+// calls in *n_pdf_tests / *n_pdf_hits.
+template <bool EXT, bool COUNT>
+DEV uint32_t estimate_direct_request(const DScene &S, const DLight &lt, const DSphere *lsp, const Isect &is, const Bsdf &bsdf, float ul0,
+                                     float ul1, float us0, float us1, F3 &so, F3 &sd, F3 &A, F3 &mo, F3 &md, F3 &Bc,
+                                     unsigned long long *n_pdf_tests, unsigned long long *n_pdf_hits) {
+    uint32_t nee_flags = 0;
+    if (EXT && lt.type == kLightInfinite) {
+        // the light-sampling half through the environment map's Distribution2D, the BSDF-sampling half whose ray contributes
+        // Le(ray) when it escapes (:209-210; k_mis marks escaped rays, k_mis_lit accepts them for an infinite light)
+        float light_pdf = 0, scattering_pdf = 0;
+        F3 wi = F3{0, 0, 0}, target = F3{0, 0, 0};
+        const F3 Li = inf_sample_li(S, lt, is.p, ul0, ul1, &wi, &light_pdf, &target);
+        if (light_pdf > 0 && !is_black(Li)) {
+            const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
+            scattering_pdf = bsdf_pdf(bsdf, is.wo, wi);
+            if (!is_black(f)) {
+                so = offset_ray_origin(is.p, is.perr, is.n, target - is.p);
+                sd = target - so;
+                A = sdiv(f * Li * power_heuristic(light_pdf, scattering_pdf), light_pdf);
+                nee_flags |= NEE_HAS_SHADOW;
+            }
+        }
+        F3 f2 = bsdf_sample_f(bsdf, is.wo, &wi, us0, us1, &scattering_pdf);
+        f2 = f2 * absdot(wi, is.sn);
+        if (!is_black(f2) && scattering_pdf > 0) {
+            const float lp = inf_pdf_li(S, lt, wi);
+            if (lp != 0) {
+                mo = offset_ray_origin(is.p, is.perr, is.n, wi);
+                md = wi;
+                Bc = sdiv(f2 * inf_le(S, lt, wi) * power_heuristic(scattering_pdf, lp), scattering_pdf);
+                nee_flags |= NEE_HAS_MIS;
+            }
+        }
+    } else if (EXT && lt.type != kLightDiffuseArea && lt.type != kLightAreaTriangle && lt.type != kLightAreaQuadric) {
+        // a delta light (integrator.cpp:150-166): light sample only, weight 1
+        F3 wi, target;
+        const F3 Li = delta_light_li(lt, is.p, &wi, &target);
+        if (!is_black(Li)) {
+            const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
+            if (!is_black(f)) {
+                // the light-side Interaction has neither normal nor error bounds: its OffsetRayOrigin is the point itself
+                // (interaction.h:73-78)
+                so = offset_ray_origin(is.p, is.perr, is.n, target - is.p);
+                sd = target - so;
+                A = sdiv(f * Li, 1.f);
+                nee_flags |= NEE_HAS_SHADOW;
+            }
+        }
+    } else {
+        // light-sampling half (integrator.cpp:117-163)
+        float light_pdf = 0, scattering_pdf = 0;
+        F3 wi = F3{0, 0, 0}, Li = F3{0, 0, 0};
+        const LightSample ps = EXT ? shape_sample(S, lt, is, ul0, ul1, &light_pdf) : sphere_sample(*lsp, is, ul0, ul1, &light_pdf);
+        if (light_pdf == 0 || length_sq(ps.p - is.p) == 0) {
+            light_pdf = 0;
+        } else {
+            wi = normalize(ps.p - is.p);
+            Li = area_light_L(lt, ps.n, -wi);
+        }
+        if (light_pdf > 0 && !is_black(Li)) {
+            const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
+            scattering_pdf = bsdf_pdf(bsdf, is.wo, wi);
+            if (!is_black(f)) {
+                // VisibilityTester -> SpawnRayTo(Interaction), interaction.h:73-78
+                so = offset_ray_origin(is.p, is.perr, is.n, ps.p - is.p);
+                const F3 target = offset_ray_origin(ps.p, ps.perr, ps.n, so - ps.p);
+                sd = target - so;
+                A = sdiv(f * Li * power_heuristic(light_pdf, scattering_pdf), light_pdf);
+                nee_flags |= NEE_HAS_SHADOW;
+            }
+        }
+        // BSDF-sampling half (integrator.cpp:165-213)
+        F3 f2 = bsdf_sample_f(bsdf, is.wo, &wi, us0, us1, &scattering_pdf);
+        f2 = f2 * absdot(wi, is.sn);
+        if (!is_black(f2) && scattering_pdf > 0) {
+            const F3 m_o = offset_ray_origin(is.p, is.perr, is.n, wi);
+            // The ray only matters if its closest hit is the sampled light (integrator.cpp:205-209), and Sphere::Pdf is the cone's
+            // pdf for ANY direction (sphere.cpp:294-306): most of these rays point away from the light. The traversal would run
+            // Sphere::Intersect on this very ray with some tMax <= inf, and every rejection of that test that depends on tMax only
+            // gets stricter as tMax shrinks (t0.hi > tMax, ts.hi > tMax): a ray the sphere test rejects at tMax = inf can never end
+            // on the light, whatever else it hits (profiles/HISTORY.md §4 "MIS rays that cannot score"). Those rays are not traced
+            // by the uninstrumented kernels (the instrumented build traces them all: the reference's ray counters are part of
+            // parity), and nothing else of this half is worked out for them — the test comes first, so a wavefront whose rays all
+            // miss skips the light's pdf, the weight and the contribution. Triangle emitters: Shape::Pdf intersects the triangle
+            // with this ray anyway (lp == 0 on a miss).
+            bool can_reach = true;
+            if (!COUNT && lt.type == kLightDiffuseArea) {
+                float t_l;
+                F3 od_l, ph_l;
+                can_reach = sphere_test(lsp ? *lsp : S.spheres[lt.sphere], m_o, wi, IILE_INF, &t_l, &od_l, &ph_l);
+            } else if (EXT && !COUNT && lt.type == kLightAreaQuadric) {  // (the same holds of Disk / Cylinder::Intersect)
+                float t_l;
+                F3 od_l, ph_l;
+                can_reach = quadric_test(S.quadrics[lt.quadric], m_o, wi, IILE_INF, &t_l, &od_l, &ph_l);
+            }
+            if (can_reach) {
+                const float lp = EXT ? shape_pdf(S, lt, is, wi, n_pdf_tests, n_pdf_hits) : sphere_pdf(*lsp, is, wi);
+                if (lp != 0) {
+                    // Li is Lemit when the MIS ray finds this light facing it
+                    mo = m_o;
+                    md = wi;
+                    Bc = sdiv(f2 * F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]} * power_heuristic(scattering_pdf, lp), scattering_pdf);
+                    nee_flags |= NEE_HAS_MIS;
+                }
+            }
+        }
+    }
+    return nee_flags;
+}
+
+// Did the BSDF-sampled ray (mo, md) of EstimateDirect, whose closest hit was primitive `prim` of light `li` at (b0, b1, b2), end
+// on the light's emitting side? (SurfaceInteraction::Le -> DiffuseAreaLight::L, integrator.cpp:205-209; the caller has checked
+// `lightIsect.primitive->GetAreaLight() == &light`)
+DEV bool mis_ray_lit(const DScene &S, int li, int prim, float b0, float b1, float b2, F3 mo, F3 md) {
+    const DLight &lt = S.lights[li];
+    Isect lis;
+    if (lt.type == kLightAreaTriangle) {
+        const float4 v0 = S.tri_verts[3 * size_t(prim)], v1 = S.tri_verts[3 * size_t(prim) + 1], v2 = S.tri_verts[3 * size_t(prim) + 2];
+        triangle_interaction(S, prim, f2b(v0.w), F3{v0.x, v0.y, v0.z}, F3{v1.x, v1.y, v1.z}, F3{v2.x, v2.y, v2.z}, md, b0, b1, b2, &lis);
+    } else {
+        // the closest hit was this sphere or quadric: redo its root selection for the hit point
+        shape_hit_interaction(S, lt.type == kLightAreaQuadric ? ~lt.quadric : lt.sphere, mo, md, &lis);
+    }
+    return lt.two_sided || dot(lis.n, -md) > 0;
+}
+
 }  // namespace iile

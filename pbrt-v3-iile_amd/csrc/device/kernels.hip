@@ -107,28 +107,13 @@ __global__ __launch_bounds__(kBlock) void k_mis_lit(DScene S, PassBuffers B, int
         const uint32_t mis = B.nee_mis[e];
         if (mis == 0) continue;
         const float4 n3 = B.nee[3 * size_t(plane) + q];
+        const int li = int(f2b(n3.w));
         bool lit = false;
-        {
-            const int li = int(f2b(n3.w));
-            if (mis == 255u) {
-                lit = S.lights[li].type == kLightInfinite;  // `else Li = light.Le(ray)`, integrator.cpp:209-210
-            } else if (int(mis) == li + 1) {
-                const DLight &lt = S.lights[li];
-                const F3 mo = F3{n2.x, n2.y, n2.z}, md = F3{n3.x, n3.y, n3.z};
-                Isect lis;
-                if (lt.type == kLightAreaTriangle) {
-                    const float4 h4 = B.mis_hit[e];  // left by k_mis
-                    const int prim = int(f2b(h4.x));
-                    const float4 v0 = S.tri_verts[3 * size_t(prim)], v1 = S.tri_verts[3 * size_t(prim) + 1],
-                                 v2 = S.tri_verts[3 * size_t(prim) + 2];
-                    triangle_interaction(S, prim, f2b(v0.w), F3{v0.x, v0.y, v0.z}, F3{v1.x, v1.y, v1.z},
-                                         F3{v2.x, v2.y, v2.z}, md, h4.y, h4.z, h4.w, &lis);
-                } else {
-                    // the closest hit was this sphere or quadric: redo its root selection for the hit point
-                    shape_hit_interaction(S, lt.type == kLightAreaQuadric ? ~lt.quadric : lt.sphere, mo, md, &lis);
-                }
-                lit = lt.two_sided || dot(lis.n, -md) > 0;
-            }
+        if (mis == 255u) {
+            lit = S.lights[li].type == kLightInfinite;  // `else Li = light.Le(ray)`, integrator.cpp:209-210
+        } else if (int(mis) == li + 1) {
+            const float4 h4 = B.mis_hit[e];  // left by k_mis
+            lit = mis_ray_lit(S, li, int(f2b(h4.x)), h4.y, h4.z, h4.w, F3{n2.x, n2.y, n2.z}, F3{n3.x, n3.y, n3.z});
         }
         B.nee_mis[e] = lit ? 1 : 0;
     }

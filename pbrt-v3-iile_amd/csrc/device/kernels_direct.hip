@@ -61,142 +61,7 @@ DEV DPcg pixel_stream(const DScene &S, const PassDesc &P, int px, int py, uint32
     return pcg_seed((static_cast<unsigned long long>(P.direct_seed + 17u * pass) << 32) + rank);
 }
 
-DEV F3 area_light_L(const DLight &lt, F3 n, F3 w) {  // DiffuseAreaLight::L, lights/diffuse.h:56-58
-    return (lt.two_sided || dot(n, w) > 0) ? F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]} : F3{0, 0, 0};
-}
-
 }  // namespace
-
-// One EstimateDirect call of UniformSampleAllLights (integrator.cpp:108-215) as a REQUEST: the shadow ray of the light-sampling
-// half with what it adds if unoccluded (A), the closest-hit ray of the BSDF-sampling half with what it adds if it ends on the
-// sampled light (Bc). The wavefront pass turns the request into an NEE record (k_mis / k_mis_lit / k_shadow resolve it), the
-// per-pixel pass for glass scenes (k_direct_tree) traces the two rays on the spot. Returns NEE_HAS_SHADOW | NEE_HAS_MIS.
-DEV uint32_t direct_light_request(const DScene &S, const DLight &lt, const Isect &is, const Bsdf &bsdf, float ul0, float ul1, float us0, float us1,
-                                  F3 &so, F3 &sd, F3 &A, F3 &mo, F3 &md, F3 &Bc) {
-    uint32_t nee_flags = 0;
-    if (lt.type == kLightInfinite) {
-        // EstimateDirect for the infinite light (integrator.cpp:108-215), as k_shade has it: the light-sampling half
-        // through the environment map's Distribution2D, the BSDF-sampling half whose ray contributes Le(ray) when it
-        // escapes (:209-210; k_mis marks escaped rays, k_mis_lit accepts them for an infinite light)
-        float light_pdf = 0, scattering_pdf = 0;
-        F3 wi = F3{0, 0, 0}, target = F3{0, 0, 0};
-        const F3 Li = inf_sample_li(S, lt, is.p, ul0, ul1, &wi, &light_pdf, &target);
-        if (light_pdf > 0 && !is_black(Li)) {
-            const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
-            scattering_pdf = bsdf_pdf(bsdf, is.wo, wi);
-            if (!is_black(f)) {
-                so = offset_ray_origin(is.p, is.perr, is.n, target - is.p);
-                sd = target - so;
-                A = sdiv(f * Li * power_heuristic(light_pdf, scattering_pdf), light_pdf);
-                nee_flags |= NEE_HAS_SHADOW;
-            }
-        }
-        F3 f2 = bsdf_sample_f(bsdf, is.wo, &wi, us0, us1, &scattering_pdf);
-        f2 = f2 * absdot(wi, is.sn);
-        if (!is_black(f2) && scattering_pdf > 0) {
-            const float lp = inf_pdf_li(S, lt, wi);
-            if (lp != 0) {
-                mo = offset_ray_origin(is.p, is.perr, is.n, wi);
-                md = wi;
-                Bc = sdiv(f2 * inf_le(S, lt, wi) * power_heuristic(scattering_pdf, lp), scattering_pdf);
-                nee_flags |= NEE_HAS_MIS;
-            }
-        }
-    } else if (lt.type != kLightDiffuseArea && lt.type != kLightAreaTriangle && lt.type != kLightAreaQuadric) {
-        // EstimateDirect for a delta light (integrator.cpp:150-166): light sample only. PointLight (lights/point.cpp:
-        // 43-52), SpotLight (spot.cpp:53-76), DistantLight (distant.cpp:50-61).
-        const F3 pos = F3{lt.pos[0], lt.pos[1], lt.pos[2]};
-        const F3 I = F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]};
-        F3 wi, target, Li;
-        if (lt.type == kLightDistant) {
-            wi = pos;
-            target = is.p + pos * (2 * lt.world_radius);
-            Li = I;
-        } else {
-            wi = normalize(pos - is.p);
-            target = pos;
-            if (lt.type == kLightSpot) {
-                const F3 w = -wi;
-                const F3 wl = normalize(F3{lt.w2l[0] * w.x + lt.w2l[1] * w.y + lt.w2l[2] * w.z,
-                                           lt.w2l[3] * w.x + lt.w2l[4] * w.y + lt.w2l[5] * w.z,
-                                           lt.w2l[6] * w.x + lt.w2l[7] * w.y + lt.w2l[8] * w.z});
-                const float cos_theta = wl.z;
-                float falloff;
-                if (cos_theta < lt.cos_total_width)
-                    falloff = 0;
-                else if (cos_theta >= lt.cos_falloff_start)
-                    falloff = 1;
-                else {
-                    const float delta = (cos_theta - lt.cos_total_width) / (lt.cos_falloff_start - lt.cos_total_width);
-                    falloff = (delta * delta) * (delta * delta);
-                }
-                Li = sdiv(I * falloff, length_sq(pos - is.p));
-            } else {
-                Li = sdiv(I, length_sq(pos - is.p));
-            }
-        }
-        if (!is_black(Li)) {
-            const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
-            if (!is_black(f)) {
-                so = offset_ray_origin(is.p, is.perr, is.n, target - is.p);
-                sd = target - so;
-                A = sdiv(f * Li, 1.f);
-                nee_flags |= NEE_HAS_SHADOW;
-            }
-        }
-    } else {
-        // EstimateDirect, light-sampling half (integrator.cpp:117-163)
-        float light_pdf = 0, scattering_pdf = 0;
-        F3 wi = F3{0, 0, 0}, Li = F3{0, 0, 0};
-        const LightSample ps = shape_sample(S, lt, is, ul0, ul1, &light_pdf);
-        if (light_pdf == 0 || length_sq(ps.p - is.p) == 0) {
-            light_pdf = 0;
-        } else {
-            wi = normalize(ps.p - is.p);
-            Li = area_light_L(lt, ps.n, -wi);
-        }
-        if (light_pdf > 0 && !is_black(Li)) {
-            const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
-            scattering_pdf = bsdf_pdf(bsdf, is.wo, wi);
-            if (!is_black(f)) {
-                so = offset_ray_origin(is.p, is.perr, is.n, ps.p - is.p);
-                const F3 target = offset_ray_origin(ps.p, ps.perr, ps.n, so - ps.p);
-                sd = target - so;
-                A = sdiv(f * Li * power_heuristic(light_pdf, scattering_pdf), light_pdf);
-                nee_flags |= NEE_HAS_SHADOW;
-            }
-        }
-        // BSDF-sampling half (integrator.cpp:165-213). A ray that the light's sphere rejects at tMax = inf can never end on the
-        // light whatever else it hits (DESIGN.md "MIS rays that cannot score": every tMax-dependent branch of Sphere::Intersect is
-        // a rejection), so its term is exactly zero and it is not queued — with nSamples = 8 that is most of the pass's rays.
-        F3 f2 = bsdf_sample_f(bsdf, is.wo, &wi, us0, us1, &scattering_pdf);
-        f2 = f2 * absdot(wi, is.sn);
-        if (!is_black(f2) && scattering_pdf > 0) {
-            const F3 m_o = offset_ray_origin(is.p, is.perr, is.n, wi);
-            bool can_reach = true;
-            if (lt.type == kLightDiffuseArea) {
-                float t_l;
-                F3 od_l, ph_l;
-                can_reach = sphere_test(S.spheres[lt.sphere], m_o, wi, IILE_INF, &t_l, &od_l, &ph_l);
-            } else if (lt.type == kLightAreaQuadric) {  // (the same holds of Disk / Cylinder::Intersect)
-                float t_l;
-                F3 od_l, ph_l;
-                can_reach = quadric_test(S.quadrics[lt.quadric], m_o, wi, IILE_INF, &t_l, &od_l, &ph_l);
-            }
-            if (can_reach) {
-                unsigned long long nt = 0, nh = 0;
-                const float lp = shape_pdf(S, lt, is, wi, &nt, &nh);
-                if (lp != 0) {
-                    mo = m_o;
-                    md = wi;
-                    Bc = sdiv(f2 * F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]} * power_heuristic(scattering_pdf, lp), scattering_pdf);
-                    nee_flags |= NEE_HAS_MIS;
-                }
-            }
-        }
-    }
-    return nee_flags;
-}
 
 // jump[2 i], jump[2 i + 1]: the stream at array i's first entry (the arrays before it hold 16 x nSamples entries of two draws
 // each: RandomSampler::StartPixel, random.cpp:62-72); entry n_arrays: the camera sample
@@ -323,7 +188,8 @@ __global__ __launch_bounds__(kBlock, IILE_DIRECT_SHADE_WAVES) void k_direct_shad
             if (valid && lit_surface) {
                 const DLight &lt = S.lights[li];
                 const float ul0 = pcg_float(ra), ul1 = pcg_float(ra), us0 = pcg_float(rb), us1 = pcg_float(rb);
-                nee_flags = direct_light_request(S, lt, is, bsdf, ul0, ul1, us0, us1, so, sd, A, mo, md, Bc);
+                unsigned long long nt = 0, nh = 0;  // (counted by the instrumented k_shade only)
+                nee_flags = estimate_direct_request<true, false>(S, lt, nullptr, is, bsdf, ul0, ul1, us0, us1, so, sd, A, mo, md, Bc, &nt, &nh);
                 emit_nee = nee_flags != 0;
             }
             const uint32_t eslot = out_take(nee_out, &B.counts[kCntNee + depth], emit_nee, pad_nee);
@@ -528,21 +394,15 @@ TREE_CALL void tree_bsdf(const DScene &S, int material, const TexDiff &td, F3 dp
 }
 TREE_CALL uint32_t tree_light_request(const DScene &S, int li, const Isect &is, const Bsdf &bsdf, float ul0, float ul1, float us0, float us1, F3 *so,
                                       F3 *sd, F3 *A, F3 *mo, F3 *md, F3 *Bc) {
-    return direct_light_request(S, S.lights[li], is, bsdf, ul0, ul1, us0, us1, *so, *sd, *A, *mo, *md, *Bc);
+    const DLight &lt = S.lights[li];
+    unsigned long long nt = 0, nh = 0;
+    return estimate_direct_request<true, false>(S, lt, nullptr, is, bsdf, ul0, ul1, us0, us1, *so, *sd, *A, *mo, *md, *Bc, &nt, &nh);
 }
 // did the BSDF-sampled ray of EstimateDirect end on light `li`, on its emitting side? (k_mis + k_mis_lit of the wavefront)
 TREE_CALL bool tree_mis_lit(const DScene &S, int li, bool hit, const HitRec &hm, F3 mo, F3 md) {
-    const DLight &lt = S.lights[li];
-    if (!hit) return lt.type == kLightInfinite;  // `else Li = light.Le(ray)`, integrator.cpp:209-210
-    const float4 w0 = S.tri_verts[3 * size_t(hm.prim)], w1 = S.tri_verts[3 * size_t(hm.prim) + 1], w2 = S.tri_verts[3 * size_t(hm.prim) + 2];
-    if (int(f2b(w2.w)) != li) return false;  // lightIsect.primitive->GetAreaLight() == &light
-    Isect lis;
-    if (f2b(w0.w) & 1u) {
-        shape_hit_interaction(S, lt.type == kLightAreaQuadric ? ~lt.quadric : lt.sphere, mo, md, &lis);
-    } else {
-        triangle_interaction(S, hm.prim, f2b(w0.w), F3{w0.x, w0.y, w0.z}, F3{w1.x, w1.y, w1.z}, F3{w2.x, w2.y, w2.z}, md, hm.b0, hm.b1, hm.b2, &lis);
-    }
-    return lt.two_sided || dot(lis.n, -md) > 0;
+    if (!hit) return S.lights[li].type == kLightInfinite;  // `else Li = light.Le(ray)`, integrator.cpp:209-210
+    if (int(f2b(S.tri_verts[3 * size_t(hm.prim) + 2].w)) != li) return false;  // lightIsect.primitive->GetAreaLight() == &light
+    return mis_ray_lit(S, li, hm.prim, hm.b0, hm.b1, hm.b2, mo, md);
 }
 // NT: the number of BSDF_TRANSMISSION | BSDF_SPECULAR lobes a BSDF of the scene can hold — 1 (glass) or 2 (an uber material's
 // pass-through and its Kt lobe): SpecularTransmit's u[0] picks among them AFTER the reflection subtree has drawn its samples, so

@@ -7,43 +7,20 @@
 namespace iile {
 
 // ---------------------------------------------------------------------------
-// DiffuseAreaLight::L (lights/diffuse.h:56-58)
-DEV F3 light_L(const DLight &lt, F3 n, F3 w) {
-    return (lt.two_sided || dot(n, w) > 0) ? F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]} : F3{0, 0, 0};
-}
-
-// ---------------------------------------------------------------------------
 // SpatialLightDistribution (core/lightdistrib.cpp:91-299): with more than one light the path
 // integrator picks the light to sample from a per-voxel distribution. The reference fills a
 // hash table lazily; a voxel's distribution is a pure function of its index, so all of them are
 // tabulated once at scene creation (k_light_distributions) and looked up densely.
 // Light::Sample_Li at an Interaction without normal or error bounds (lightdistrib.cpp:258-262)
 DEV F3 sample_li_plain(const DScene &S, const DLight &lt, F3 po, float u0, float u1, float *pdf) {
-    const F3 pos = F3{lt.pos[0], lt.pos[1], lt.pos[2]};
-    const F3 I = F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]};
     *pdf = 1;
     if (lt.type == kLightInfinite) {
         F3 wi, target;
         return inf_sample_li(S, lt, po, u0, u1, &wi, pdf, &target);
     }
-    if (lt.type == kLightDistant) return I;
-    if (lt.type == kLightPoint) return sdiv(I, length_sq(pos - po));
-    if (lt.type == kLightSpot) {
-        const F3 w = -normalize(pos - po);
-        const F3 wl = normalize(F3{lt.w2l[0] * w.x + lt.w2l[1] * w.y + lt.w2l[2] * w.z,
-                                   lt.w2l[3] * w.x + lt.w2l[4] * w.y + lt.w2l[5] * w.z,
-                                   lt.w2l[6] * w.x + lt.w2l[7] * w.y + lt.w2l[8] * w.z});
-        const float cos_theta = wl.z;
-        float falloff;
-        if (cos_theta < lt.cos_total_width)
-            falloff = 0;
-        else if (cos_theta >= lt.cos_falloff_start)
-            falloff = 1;
-        else {
-            const float delta = (cos_theta - lt.cos_total_width) / (lt.cos_falloff_start - lt.cos_total_width);
-            falloff = (delta * delta) * (delta * delta);
-        }
-        return sdiv(I * falloff, length_sq(pos - po));
+    if (lt.type == kLightPoint || lt.type == kLightSpot || lt.type == kLightDistant) {
+        F3 wi, target;
+        return delta_light_li(lt, po, &wi, &target);
     }
     Isect ref;  // DiffuseAreaLight::Sample_Li, lights/diffuse.cpp:68-81
     ref.p = po;
@@ -55,7 +32,7 @@ DEV F3 sample_li_plain(const DScene &S, const DLight &lt, F3 po, float u0, float
         return F3{0, 0, 0};
     }
     const F3 wi = normalize(ps.p - po);
-    return light_L(lt, ps.n, -wi);
+    return area_light_L(lt, ps.n, -wi);
 }
 DEV float lerp_f(float t, float a, float b) { return (1 - t) * a + t * b; }  // pbrt.h:414
 // SpatialLightDistribution::ComputeDistribution (lightdistrib.cpp:228-299), one thread per voxel.
@@ -175,7 +152,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
     unsigned long long n_nee = 0, n_term = 0, n_pdf_tests = 0, n_pdf_hits = 0;
 #ifdef IILE_SHADE_STAMPS
     // diagnostic build only: wave cycles (s_memtime) per section of a round, summed per wavefront, added to
-    // DCounters::path_length[0..7] at the end: 0 regroup, 1 loads + Halton, 2 interaction + BSDF, 3 light half, 4 BSDF half,
+    // DCounters::path_length[0..7] at the end: 0 regroup, 1 loads + Halton, 2 interaction + BSDF, 3 EstimateDirect, 4 end of section A,
     // 5 record stores, 6 continuation, 7 next-ray store
     unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stamp_t = __builtin_amdgcn_s_memtime();
@@ -321,7 +298,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                 // integrator leaves out the camera ray's own vertex (iispt_d.cpp:116-123)
                 if (((bounce == 0 && !(EXT && S.probe_mode)) || prev_specular) && light >= 0) {
                     const float4 L4 = B.L[pid];
-                    const F3 L = F3{L4.x, L4.y, L4.z} + beta * light_L(S.lights[light], is.n, -ray_d);
+                    const F3 L = F3{L4.x, L4.y, L4.z} + beta * area_light_L(S.lights[light], is.n, -ray_d);
                     B.L[pid] = make_float4(L.x, L.y, L.z, 0);
                 }
                 if (bounce < S.max_depth) {
@@ -383,152 +360,10 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                             }
                             const DLight &lt = EXT ? S.lights[li] : lt_u;
                             const DSphere &lsp = EXT ? S.spheres[lt.sphere] : lsp_u;
-                            if (EXT && lt.type == kLightInfinite) {
-                                // EstimateDirect for the infinite light (integrator.cpp:108-215): both halves; the
-                                // BSDF-sampled ray contributes Le(ray) when it escapes (:209-210)
-                                const float ul0 = u_nee[0], ul1 = u_nee[1], us0 = u_nee[2], us1 = u_nee[3];
-                                dim += 4;
-                                float light_pdf = 0, scattering_pdf = 0;
-                                F3 wi = F3{0, 0, 0}, target = F3{0, 0, 0};
-                                const F3 Li = inf_sample_li(S, lt, is.p, ul0, ul1, &wi, &light_pdf, &target);
-                                if (light_pdf > 0 && !is_black(Li)) {
-                                    const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
-                                    scattering_pdf = bsdf_pdf(bsdf, is.wo, wi);
-                                    if (!is_black(f)) {
-                                        so = offset_ray_origin(is.p, is.perr, is.n, target - is.p);
-                                        sd = target - so;
-                                        const float weight = power_heuristic(light_pdf, scattering_pdf);
-                                        A = sdiv(f * Li * weight, light_pdf);
-                                        nee_flags |= NEE_HAS_SHADOW;
-                                    }
-                                }
-                                F3 f2 = bsdf_sample_f(bsdf, is.wo, &wi, us0, us1, &scattering_pdf);
-                                f2 = f2 * absdot(wi, is.sn);
-                                if (!is_black(f2) && scattering_pdf > 0) {
-                                    const float lp = inf_pdf_li(S, lt, wi);
-                                    if (lp != 0) {
-                                        const float weight = power_heuristic(scattering_pdf, lp);
-                                        mo = offset_ray_origin(is.p, is.perr, is.n, wi);
-                                        md = wi;
-                                        // Li is Le(ray) when the MIS ray escapes the scene
-                                        Bc = sdiv(f2 * inf_le(S, lt, wi) * weight, scattering_pdf);
-                                        nee_flags |= NEE_HAS_MIS;
-                                    }
-                                }
-                            } else if (EXT && lt.type != kLightDiffuseArea && lt.type != kLightAreaTriangle && lt.type != kLightAreaQuadric) {
-                                // EstimateDirect for a delta light (integrator.cpp:150-166): light sample
-                                // only, weight 1. Sample_Li of PointLight (lights/point.cpp:43-52),
-                                // SpotLight (spot.cpp:53-76), DistantLight (distant.cpp:50-61).
-                                dim += 4;  // uLight and uScattering are drawn all the same
-                                const F3 pos = F3{lt.pos[0], lt.pos[1], lt.pos[2]};
-                                const F3 I = F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]};
-                                F3 wi, target, Li;
-                                if (lt.type == kLightDistant) {
-                                    wi = pos;                                     // wLight
-                                    target = is.p + pos * (2 * lt.world_radius);  // pOutside
-                                    Li = I;
-                                } else {
-                                    wi = normalize(pos - is.p);
-                                    target = pos;  // pLight
-                                    if (lt.type == kLightSpot) {  // Falloff(-wi)
-                                        const F3 w = -wi;
-                                        const F3 wl = normalize(F3{lt.w2l[0] * w.x + lt.w2l[1] * w.y + lt.w2l[2] * w.z,
-                                                                   lt.w2l[3] * w.x + lt.w2l[4] * w.y + lt.w2l[5] * w.z,
-                                                                   lt.w2l[6] * w.x + lt.w2l[7] * w.y + lt.w2l[8] * w.z});
-                                        const float cos_theta = wl.z;
-                                        float falloff;
-                                        if (cos_theta < lt.cos_total_width)
-                                            falloff = 0;
-                                        else if (cos_theta >= lt.cos_falloff_start)
-                                            falloff = 1;
-                                        else {
-                                            const float delta =
-                                                (cos_theta - lt.cos_total_width) / (lt.cos_falloff_start - lt.cos_total_width);
-                                            falloff = (delta * delta) * (delta * delta);
-                                        }
-                                        Li = sdiv(I * falloff, length_sq(pos - is.p));
-                                    } else {
-                                        Li = sdiv(I, length_sq(pos - is.p));
-                                    }
-                                }
-                                if (!is_black(Li)) {
-                                    const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
-                                    if (!is_black(f)) {
-                                        // the light-side Interaction has neither normal nor error bounds:
-                                        // its OffsetRayOrigin is the point itself (interaction.h:73-78)
-                                        so = offset_ray_origin(is.p, is.perr, is.n, target - is.p);
-                                        sd = target - so;
-                                        A = sdiv(f * Li, 1.f);
-                                        nee_flags |= NEE_HAS_SHADOW;
-                                    }
-                                }
-                            } else {
-                                const float ul0 = u_nee[0], ul1 = u_nee[1], us0 = u_nee[2], us1 = u_nee[3];
-                                dim += 4;
-                                // EstimateDirect, light-sampling half (integrator.cpp:117-163)
-                                float light_pdf = 0, scattering_pdf = 0;
-                                F3 wi = F3{0, 0, 0}, Li = F3{0, 0, 0};
-                                LightSample ps = EXT ? shape_sample(S, lt, is, ul0, ul1, &light_pdf)
-                                                     : sphere_sample(lsp, is, ul0, ul1, &light_pdf);
-                                if (light_pdf == 0 || length_sq(ps.p - is.p) == 0) {
-                                    light_pdf = 0;
-                                } else {
-                                    wi = normalize(ps.p - is.p);
-                                    Li = light_L(lt, ps.n, -wi);
-                                }
-                                if (light_pdf > 0 && !is_black(Li)) {
-                                    F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
-                                    scattering_pdf = bsdf_pdf(bsdf, is.wo, wi);
-                                    if (!is_black(f)) {
-                                        // VisibilityTester -> SpawnRayTo(Interaction), interaction.h:73-78
-                                        so = offset_ray_origin(is.p, is.perr, is.n, ps.p - is.p);
-                                        F3 target = offset_ray_origin(ps.p, ps.perr, ps.n, so - ps.p);
-                                        sd = target - so;
-                                        const float weight = power_heuristic(light_pdf, scattering_pdf);
-                                        A = sdiv(f * Li * weight, light_pdf);
-                                        nee_flags |= NEE_HAS_SHADOW;
-                                    }
-                                }
-                                SHADE_STAMP(3);
-                                // BSDF-sampling half (integrator.cpp:165-213)
-                                F3 f2 = bsdf_sample_f(bsdf, is.wo, &wi, us0, us1, &scattering_pdf);
-                                f2 = f2 * absdot(wi, is.sn);
-                                if (!is_black(f2) && scattering_pdf > 0) {
-                                    mo = offset_ray_origin(is.p, is.perr, is.n, wi);
-                                    md = wi;
-                                    // The ray only matters if its closest hit is the sampled light (integrator.cpp:205-209),
-                                    // and Sphere::Pdf is the cone's pdf for ANY direction (sphere.cpp:294-306): most of these
-                                    // rays point away from the light. The traversal would run Sphere::Intersect on this very
-                                    // ray with some tMax <= inf, and every rejection of that test that depends on tMax only
-                                    // gets stricter as tMax shrinks (t0.hi > tMax, ts.hi > tMax): a ray the sphere test
-                                    // rejects at tMax = inf can never end on the light, whatever else it hits. Those rays are
-                                    // not traced by the uninstrumented kernels (the instrumented build traces them all: the
-                                    // reference's ray counters are part of parity), and nothing else of this half is worked
-                                    // out for them — the test comes first, so a wavefront whose rays all miss skips the light's
-                                    // pdf, the weight and the contribution. Triangle emitters: Shape::Pdf intersects the
-                                    // triangle with this ray anyway (lp == 0 on a miss).
-                                    bool can_reach = true;
-                                    if (!COUNT && lt.type == kLightDiffuseArea) {
-                                        float t_l;
-                                        F3 od_l, ph_l;
-                                        can_reach = sphere_test(lsp, mo, md, IILE_INF, &t_l, &od_l, &ph_l);
-                                    } else if (EXT && !COUNT && lt.type == kLightAreaQuadric) {  // (the same holds of Disk / Cylinder::Intersect)
-                                        float t_l;
-                                        F3 od_l, ph_l;
-                                        can_reach = quadric_test(S.quadrics[lt.quadric], mo, md, IILE_INF, &t_l, &od_l, &ph_l);
-                                    }
-                                    if (can_reach) {
-                                        const float lp = EXT ? shape_pdf(S, lt, is, wi, &n_pdf_tests, &n_pdf_hits)
-                                                             : sphere_pdf(lsp, is, wi);
-                                        if (lp != 0) {
-                                            const float weight = power_heuristic(scattering_pdf, lp);
-                                            // Li is Lemit when the MIS ray finds this light facing it
-                                            Bc = sdiv(f2 * F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]} * weight, scattering_pdf);
-                                            nee_flags |= NEE_HAS_MIS;
-                                        }
-                                    }
-                                }
-                            }
+                            dim += 4;  // uLight and uScattering, drawn for every kind of light
+                            nee_flags = estimate_direct_request<EXT, COUNT>(S, lt, &lsp, is, bsdf, u_nee[0], u_nee[1], u_nee[2], u_nee[3], so, sd,
+                                                                            A, mo, md, Bc, &n_pdf_tests, &n_pdf_hits);
+                            SHADE_STAMP(3);
                             nee_light = uint32_t(li);
                             // a record with neither ray adds nothing to L; only the instrumented build needs it (zero_radiance)
                             emit_nee = COUNT || nee_flags != 0;

@@ -15,7 +15,7 @@ scene = b.HostScene(xres=1920, yres=1080, spp=64)
 gpu = b.GpuScene(scene)
 gpu.render()
 _, st = gpu.render(want_stats=True, time_kernels=2)
-names = ["regroup chunk", "loads + 4 Halton dims", "interaction + BSDF set-up", "light-sampling half", "BSDF-sampling half", "NEE record stores",
+names = ["regroup chunk", "loads + 4 Halton dims", "interaction + BSDF set-up", "EstimateDirect (both halves)", "end of the interaction section", "NEE record stores",
          "continuation (2 Halton dims, Sample_f, RR)", "next-ray store"]
 cyc = [int(x) for x in st["path_length"]]
 tot = sum(cyc) or 1
