@@ -13,7 +13,6 @@
 #include <string>
 #include <limits>
 #include <map>
-#include <numeric>
 #include <vector>
 
 #include "../../../include/iile_gpu.h"
@@ -85,10 +84,6 @@ struct iile_scene {
     const float *probe_filter_table = nullptr;
     uint32_t *flag_count = nullptr;  // whole-number film positions (PassBuffers::flag_count / flag_rec)
     float *flag_rec = nullptr;
-    float *flag_host = nullptr;      // pinned staging for the records (count first)
-    size_t flag_host_floats = 0;
-    hipStream_t aux_stream = nullptr;  // copies the flagged list to the host beside a running pass
-    hipEvent_t ev_flags = nullptr;     // recorded after the first k_extend of a pass: the list is complete
     void *probe_block = nullptr;  // cameras + aux + outputs of the last probe batch
     size_t probe_block_bytes = 0;
     void *film_block = nullptr;
@@ -117,7 +112,7 @@ struct iile_scene {
     uint32_t patch_cap_override = 0;     // iile_test_patch_capacity: hits / entries capacity forced by a test
     bool overflow_unchecked = false;     // an asynchronous render left patch.counters[2] unread
     hipStream_t overflow_stream = nullptr;
-    // grow-only device scratch of the host-side film finish (IILE_DEBUG_HOST_FILM_FINISH: index lists in, gathered values out)
+    // grow-only device scratch of the IISPT slices (scratch_reserve / scratch_take)
     char *scratch = nullptr;
     size_t scratch_cap = 0, scratch_used = 0;
 };
@@ -421,7 +416,6 @@ int run_pass(iile_scene *sc, const DScene &S, int max_depth, const PassDesc &P_i
     for (int b = 0; b <= last_bounce; ++b) {
         rc = timed_launch(1, [&] { launch_extend(S, P, B, b, B.queue_cap, cfg); });
         if (rc) return rc;
-        if (b == 0 && B.flag_count && sc->ev_flags) HIP_TRY(hipEventRecord(sc->ev_flags, cfg.stream));
         if (S.has_infinite) {  // escaped rays see the infinite lights (path.cpp:97-99)
             rc = timed_launch(6, [&] { launch_miss(S, B, b, B.queue_cap, cfg); });
             if (rc) return rc;
@@ -490,7 +484,7 @@ struct DevBuf {
     }
 };
 
-// Device scratch for the finish: reserve once per use (may reallocate: nothing of an earlier use is live), then carve.
+// Device scratch of the IISPT slices: reserve once per use (may reallocate: nothing of an earlier use is live), then carve.
 int scratch_reserve(iile_scene *sc, size_t bytes, hipStream_t stream) {
     sc->scratch_used = 0;
     if (bytes <= sc->scratch_cap) return IILE_OK;
@@ -508,16 +502,6 @@ T *scratch_take(iile_scene *sc, size_t n) {
     char *p = sc->scratch + sc->scratch_used;
     sc->scratch_used += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~size_t(255);
     return reinterpret_cast<T *>(p);
-}
-template <typename T>
-size_t scratch_bytes(size_t n) {
-    return (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~size_t(255);
-}
-template <typename T>
-int scratch_put(iile_scene *sc, const std::vector<T> &h, hipStream_t stream, T **dev) {
-    *dev = scratch_take<T>(sc, h.size());
-    if (!h.empty()) HIP_TRY(hipMemcpyAsync(*dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-    return IILE_OK;
 }
 
 // ---- iile_scene_create: one refusal pass, then one builder per table of DScene; first the translations both apply ------
@@ -1079,7 +1063,7 @@ int build_camera_film(iile_scene *sc, const iile_scene_desc &d) {
 }
 
 // What a render needs besides the scene: the traversal stacks' spill buffers, the NEE stream and its events, the timing
-// events, the flagged-sample records and the stream that copies them out.
+// events and the flagged-sample records.
 int build_runtime(iile_scene *sc, const iile_scene_desc &) {
     int rc = scene_alloc(sc, size_t(max_traversal_threads(sc->n_cus)) * sizeof(int), &sc->spill, "hipMalloc(spill) failed");
     if (!rc) rc = scene_alloc(sc, size_t(max_traversal_threads(sc->n_cus)) * sizeof(int), &sc->spill_nee, "hipMalloc(spill) failed");
@@ -1092,9 +1076,6 @@ int build_runtime(iile_scene *sc, const iile_scene_desc &) {
             hipEventCreateWithFlags(&sc->ev_nee[i], hipEventDisableTiming) != hipSuccess)
             return fail(IILE_ERR_HIP, "hipEventCreate failed");
     if (hipEventCreate(&sc->ev_begin) != hipSuccess || hipEventCreate(&sc->ev_end) != hipSuccess) return fail(IILE_ERR_HIP, "hipEventCreate failed");
-    if (hipStreamCreateWithFlags(&sc->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&sc->ev_flags, hipEventDisableTiming) != hipSuccess)
-        return fail(IILE_ERR_HIP, "hipStreamCreate / hipEventCreate failed");
     return IILE_OK;
 }
 
@@ -1275,9 +1256,6 @@ void iile_scene_destroy(iile_scene *sc) {
     if (sc->film_add_buf) (void)hipFree(sc->film_add_buf);
     if (sc->scratch) (void)hipFree(sc->scratch);
     if (sc->wide_block) (void)hipFree(sc->wide_block);
-    if (sc->flag_host) (void)hipHostFree(sc->flag_host);
-    if (sc->aux_stream) (void)hipStreamDestroy(sc->aux_stream);
-    if (sc->ev_flags) (void)hipEventDestroy(sc->ev_flags);
     if (sc->nee_stream) (void)hipStreamDestroy(sc->nee_stream);
     for (int i = 0; i < 16; ++i) {
         if (sc->ev_shade[i]) (void)hipEventDestroy(sc->ev_shade[i]);
@@ -1293,401 +1271,6 @@ void iile_scene_destroy(iile_scene *sc) {
     if (sc->ev_end) (void)hipEventDestroy(sc->ev_end);
     delete sc;
 }
-
-namespace {
-// The one-pixel box film's exact finish. k_film_accumulate / k_film_resolve give every pixel the sum of its own
-// samples (plus the k = 0 zero-offset splats) — all there is unless a sample's film position is a whole number, when
-// FilmTile::AddSample (film.h:159-188) also adds it to a neighbouring pixel, in sample order inside its tile. The
-// generation code listed those samples (rare: ~1e-4 of them where pixel coordinates pass 1024); here every pixel
-// they touch is recomputed the way the reference sums it: per contributing tile, own samples and neighbours'
-// samples merged in generation order (pixel-major, then k), tiles added in index order (MergeFilmTile, film.cpp:135-148;
-// the reference merges in completion order, the oracle and this in index order). Radiances come from re-rendering
-// the few paths involved through the explicit-list pass (bitwise the same values).
-struct Flagged {
-    int px, py, k;
-    float pfx, pfy;
-    uint32_t pid;
-    int tile, pix;  // tile index and row-major pixel rank inside the tile: generation order = (tile, pix, k)
-    bool plain_k0;  // sample 0 with exact zero offsets only: k_film_resolve adds it to its neighbours by itself
-};
-struct PatchDest {
-    uint32_t film_index;
-    int qx, qy, tile, pix;
-    bool own_in_pass, need_own;  // its own tile is rendered by this pass; it receives from a pixel generated before it there
-    uint32_t own_slot;           // index into tile_rgbw
-    size_t first, last;          // its range of `hits`
-    size_t own_first;            // first of its own samples in the gather list
-};
-// What patch_prepare works out on the host for one pass. It needs only the pass's list of flagged samples, complete once
-// the pass's first k_extend has run — i.e. while the GPU is still busy with the rest of the pass.
-struct PatchPlan {
-    bool active = false;
-    int k_begin = 0, k_end = 0, slot0 = 0;
-    std::vector<Flagged> fl;
-    std::vector<std::pair<uint32_t, int>> hits;  // (destination film pixel, flagged sample) by destination, then generation order
-    std::vector<PatchDest> dests;
-    std::vector<uint32_t> list_pid;              // path ids (of this pass) whose radiance is needed
-    std::vector<int> list_of_flag;
-};
-// One exact FilmTile sum: what tile `tile` adds to film pixel `film_index` (rgb contribSum, weight sum)
-struct PatchEntry {
-    uint32_t film_index;
-    int tile;
-    float r, g, b, w;
-    bool nonplain;  // involves a sample that k_film_resolve does not place
-};
-struct PatchTimer {
-    bool on = false;   // (laps of the host-side film finish to stderr: flip when debugging IILE_DEBUG_HOST_FILM_FINISH)
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    void lap(const char *what) {
-        if (!on) return;
-        auto t1 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[patch] %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
-};
-
-int patch_prepare(iile_scene *sc, const DScene &S, const PassDesc &Pf, hipStream_t copy_stream, PatchPlan *plan) {
-    PatchTimer tm;
-    plan->active = false;
-    plan->k_begin = Pf.k0, plan->k_end = Pf.k0 + Pf.kc, plan->slot0 = Pf.slot0;
-    uint32_t n_flag = 0;
-    if (sc->flag_host_floats < 64) {  // pinned staging: count first, then the records
-        void *hp = nullptr;
-        HIP_TRY(hipHostMalloc(&hp, (size_t(1) << 16) * sizeof(float), hipHostMallocDefault));
-        if (sc->flag_host) (void)hipHostFree(sc->flag_host);
-        sc->flag_host = static_cast<float *>(hp);
-        sc->flag_host_floats = size_t(1) << 16;
-    }
-    HIP_TRY(hipMemcpyAsync(sc->flag_host, sc->flag_count, sizeof(uint32_t), hipMemcpyDeviceToHost, copy_stream));
-    HIP_TRY(hipStreamSynchronize(copy_stream));
-    std::memcpy(&n_flag, sc->flag_host, sizeof(n_flag));
-    std::vector<Flagged> &fl = plan->fl;
-    std::vector<std::pair<uint32_t, int>> &hits = plan->hits;
-    std::vector<PatchDest> &dests = plan->dests;
-    fl.clear(), hits.clear(), dests.clear(), plan->list_pid.clear(), plan->list_of_flag.clear();
-    if (n_flag == 0) return IILE_OK;
-    if (n_flag > kMaxFlagged) return fail(IILE_ERR_UNSUPPORTED, "more than 2^20 camera samples with whole-number film positions in one pass");
-    if (sc->flag_host_floats < size_t(n_flag) * 6) {
-        void *hp = nullptr;
-        const size_t want = size_t(n_flag) * 6 * 2;
-        HIP_TRY(hipHostMalloc(&hp, want * sizeof(float), hipHostMallocDefault));
-        if (sc->flag_host) (void)hipHostFree(sc->flag_host);
-        sc->flag_host = static_cast<float *>(hp);
-        sc->flag_host_floats = want;
-    }
-    HIP_TRY(hipMemcpyAsync(sc->flag_host, sc->flag_rec, size_t(n_flag) * 6 * sizeof(float), hipMemcpyDeviceToHost, copy_stream));
-    HIP_TRY(hipStreamSynchronize(copy_stream));
-    const float *rec = sc->flag_host;
-    tm.lap("download records");
-    const int ntx = Pf.n_tiles_x;
-    auto tile_of = [&](int x, int y, int *pix) {
-        const int tx = (x - S.samp_x0) / 16, ty = (y - S.samp_y0) / 16;
-        *pix = (y - S.samp_y0 - ty * 16) * 16 + (x - S.samp_x0 - tx * 16);
-        return ty * ntx + tx;
-    };
-    fl.resize(n_flag);
-    for (uint32_t i = 0; i < n_flag; ++i) {
-        uint32_t u[6];
-        std::memcpy(u, rec + 6 * size_t(i), sizeof(u));
-        Flagged &f = fl[i];
-        f.px = int(u[0]), f.py = int(u[1]), f.k = int(u[2] & 0x3fffffffu);
-        f.pfx = rec[6 * size_t(i) + 3], f.pfy = rec[6 * size_t(i) + 4];
-        f.pid = u[5];
-        f.tile = tile_of(f.px, f.py, &f.pix);
-        const bool zero_x = (u[2] >> 30) & 1u, zero_y = (u[2] >> 31) & 1u;
-        const bool whole_x = f.pfx == float(f.px) || f.pfx == float(f.px + 1), whole_y = f.pfy == float(f.py) || f.pfy == float(f.py + 1);
-        f.plain_k0 = f.k == 0 && (!whole_x || zero_x) && (!whole_y || zero_y);
-    }
-    auto gen_key = [&](int i) { return (uint64_t(uint32_t(fl[i].tile)) << 40) | (uint64_t(uint32_t(fl[i].pix)) << 32) | uint64_t(uint32_t(fl[i].k)); };
-    // every (destination pixel, flagged sample of another pixel that lands in it)
-    const int fw = S.crop_x1 - S.crop_x0;
-    hits.reserve(size_t(n_flag) * 2);
-    const float r = 0.5f;
-    for (int i = 0; i < int(fl.size()); ++i) {
-        const Flagged &f = fl[i];
-        const int tx = f.tile % ntx, ty = f.tile / ntx;
-        const int sx0 = S.samp_x0 + tx * 16, sy0 = S.samp_y0 + ty * 16;
-        const int sx1 = std::min(sx0 + 16, S.samp_x1), sy1 = std::min(sy0 + 16, S.samp_y1);
-        // Film::GetFilmTile bounds of the sample's tile, film.cpp:92-103
-        const int fx0 = std::max(int(std::ceil(float(sx0) - 0.5f - r)), S.crop_x0), fx1 = std::min(int(std::floor(float(sx1) - 0.5f + r)) + 1, S.crop_x1);
-        const int fy0 = std::max(int(std::ceil(float(sy0) - 0.5f - r)), S.crop_y0), fy1 = std::min(int(std::floor(float(sy1) - 0.5f + r)) + 1, S.crop_y1);
-        const float dxf = f.pfx - 0.5f, dyf = f.pfy - 0.5f;
-        const int ax0 = std::max(int(std::ceil(dxf - r)), fx0), ax1 = std::min(int(std::floor(dxf + r)) + 1, fx1);
-        const int ay0 = std::max(int(std::ceil(dyf - r)), fy0), ay1 = std::min(int(std::floor(dyf + r)) + 1, fy1);
-        for (int y = ay0; y < ay1; ++y)
-            for (int x = ax0; x < ax1; ++x)
-                if (x != f.px || y != f.py) hits.emplace_back(uint32_t(y - S.crop_y0) * uint32_t(fw) + uint32_t(x - S.crop_x0), i);
-    }
-    if (hits.empty()) return IILE_OK;
-    std::sort(hits.begin(), hits.end(), [&](const std::pair<uint32_t, int> &a, const std::pair<uint32_t, int> &b) {
-        return a.first != b.first ? a.first < b.first : gen_key(a.second) < gen_key(b.second);
-    });
-    tm.lap("destinations");
-    // which radiances are needed: every flagged sample that lands somewhere else, and all own samples of a pixel that
-    // receives from a pixel generated before it in its own tile
-    const int n_k = Pf.kc;
-    plan->list_of_flag.assign(fl.size(), -1);
-    for (size_t a = 0; a < hits.size();) {
-        size_t b = a;
-        while (b < hits.size() && hits[b].first == hits[a].first) ++b;
-        if (Pf.n_pass_tiles == Pf.n_owned_tiles) {
-            // the pass is the whole frame: a pixel reached only by samples k_film_resolve places itself needs nothing
-            bool only_plain = true;
-            for (size_t h = a; h < b; ++h) only_plain = only_plain && fl[hits[h].second].plain_k0;
-            if (only_plain) {
-                a = b;
-                continue;
-            }
-        }
-        PatchDest d;
-        d.film_index = hits[a].first;
-        d.first = a, d.last = b;
-        d.qx = S.crop_x0 + int(d.film_index % uint32_t(fw));
-        d.qy = S.crop_y0 + int(d.film_index / uint32_t(fw));
-        const bool in_bounds = d.qx >= S.samp_x0 && d.qx < S.samp_x1 && d.qy >= S.samp_y0 && d.qy < S.samp_y1;
-        d.tile = in_bounds ? tile_of(d.qx, d.qy, &d.pix) : -1;
-        d.own_in_pass = false;
-        d.own_slot = 0;
-        if (in_bounds && sc->slot_of(d.tile) >= 0) {
-            const int slot = sc->slot_of(d.tile);
-            d.own_in_pass = slot >= Pf.slot0 && slot < Pf.slot0 + Pf.n_pass_tiles;
-            d.own_slot = uint32_t(slot) * 256u + uint32_t(d.pix);
-        }
-        d.need_own = false;
-        d.own_first = 0;
-        for (size_t h = a; h < b; ++h) {
-            const int i = hits[h].second;
-            if (plan->list_of_flag[i] < 0) {
-                plan->list_of_flag[i] = int(plan->list_pid.size());
-                plan->list_pid.push_back(fl[i].pid);
-            }
-            if (d.own_in_pass && fl[i].tile == d.tile && fl[i].pix < d.pix) d.need_own = true;
-        }
-        if (!(d.qx >= S.pb_x0 && d.qx < S.pb_x1 && d.qy >= S.pb_y0 && d.qy < S.pb_y1)) d.need_own = false;   // (no samples of its own: k_patch_dests)
-        dests.push_back(d);
-        a = b;
-    }
-    (void)n_k;  // (the own samples of need_own pixels are summed on the device: k_patch_own)
-    if (dests.empty()) return IILE_OK;
-    tm.lap("lists");
-    if (tm.on) std::fprintf(stderr, "[patch] pass at slot %d: %u flagged samples, %zu pixels reached, %zu radiances to gather\n", Pf.slot0, n_flag, dests.size(), plan->list_pid.size());
-    plan->active = true;
-    return IILE_OK;
-}
-
-// After the pass's film accumulation: the exact sum every tile of this pass adds to every pixel reached by a flagged sample.
-// Everything runs on the render's stream (no null-stream work, no device-wide synchronisation).
-int patch_pass_finish(iile_scene *sc, const DScene &S, PatchPlan *plan, std::vector<PatchEntry> *entries, hipStream_t stream) {
-    if (!plan->active) return IILE_OK;
-    PatchTimer tm;
-    const std::vector<Flagged> &fl = plan->fl;
-    const std::vector<std::pair<uint32_t, int>> &hits = plan->hits;
-    const int n_k = plan->k_end - plan->k_begin;
-    std::vector<uint32_t> own_idx;
-    // need_own pixels: their own-tile sum is taken on the device (own samples never leave HBM)
-    std::vector<uint32_t> no_local, no_range, no_pid;
-    for (const PatchDest &d : plan->dests) {
-        if (d.own_in_pass && !d.need_own) own_idx.push_back(d.own_slot);
-        if (d.need_own) {
-            no_local.push_back(d.own_slot - uint32_t(plan->slot0) * 256u);
-            no_range.push_back(uint32_t(no_pid.size()));
-            uint32_t split = 0;
-            bool split_set = false;
-            for (size_t h = d.first; h < d.last; ++h) {
-                const Flagged &f = fl[hits[h].second];
-                if (f.tile != d.tile) continue;
-                if (!split_set && f.pix > d.pix) {
-                    split = uint32_t(no_pid.size());
-                    split_set = true;
-                }
-                no_pid.push_back(f.pid);
-            }
-            no_range.push_back(split_set ? split : uint32_t(no_pid.size()));
-            no_range.push_back(uint32_t(no_pid.size()));
-        }
-    }
-    std::vector<float4> L, own, no_sum;
-    L.resize(plan->list_pid.size());
-    own.resize(own_idx.size());
-    no_sum.resize(no_local.size());
-    LaunchCfg cfg{sc->n_cus, stream, false};
-    int rc;
-    {
-        rc = scratch_reserve(sc, scratch_bytes<uint32_t>(plan->list_pid.size()) + scratch_bytes<float4>(L.size()) +
-                                     scratch_bytes<uint32_t>(own_idx.size()) + scratch_bytes<float4>(own.size()) +
-                                     scratch_bytes<uint32_t>(no_local.size()) + scratch_bytes<uint32_t>(no_range.size()) +
-                                     scratch_bytes<uint32_t>(no_pid.size()) + scratch_bytes<float4>(no_sum.size()), stream);
-        if (rc) return rc;
-        uint32_t *di = nullptr, *dj = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-        if ((rc = scratch_put(sc, plan->list_pid, stream, &di))) return rc;
-        float4 *dv = scratch_take<float4>(sc, L.size()), *dw = nullptr, *dn = nullptr;
-        launch_gather4(sc->pb.L, di, int(plan->list_pid.size()), dv, cfg);
-        if (!own_idx.empty()) {
-            if ((rc = scratch_put(sc, own_idx, stream, &dj))) return rc;
-            dw = scratch_take<float4>(sc, own.size());
-            launch_gather4(sc->fb.tile_rgbw, dj, int(own_idx.size()), dw, cfg);
-        }
-        if (!no_local.empty()) {
-            if ((rc = scratch_put(sc, no_local, stream, &d1)) || (rc = scratch_put(sc, no_range, stream, &d2)) ||
-                (rc = scratch_put(sc, no_pid, stream, &d3)))
-                return rc;
-            dn = scratch_take<float4>(sc, no_sum.size());
-            launch_patch_own(S, sc->pb.L, int(no_local.size()), d1, d2, d3, n_k, dn, cfg);
-        }
-        HIP_TRY(hipGetLastError());
-        if (!L.empty()) HIP_TRY(hipMemcpyAsync(L.data(), dv, L.size() * sizeof(float4), hipMemcpyDeviceToHost, stream));
-        if (!own.empty()) HIP_TRY(hipMemcpyAsync(own.data(), dw, own.size() * sizeof(float4), hipMemcpyDeviceToHost, stream));
-        if (!no_sum.empty()) HIP_TRY(hipMemcpyAsync(no_sum.data(), dn, no_sum.size() * sizeof(float4), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    tm.lap("gathers");
-    for (float4 &v : L) {  // guard_radiance (kernels.hip)
-        const float y = 0.212671f * v.x + 0.715160f * v.y + 0.072169f * v.z;
-        if (std::isnan(v.x) || std::isnan(v.y) || std::isnan(v.z) || double(y) < -1e-5 || std::isinf(y)) v.x = v.y = v.z = 0.f;
-        const float y2 = 0.212671f * v.x + 0.715160f * v.y + 0.072169f * v.z;
-        if (y2 > S.max_sample_luminance) {
-            const float sc2 = S.max_sample_luminance / y2;
-            v.x *= sc2, v.y *= sc2, v.z *= sc2;
-        }
-    }
-    size_t own_at = 0, no_at = 0;
-    for (const PatchDest &d : plan->dests) {
-        float4 own_sum = make_float4(0, 0, 0, 0);
-        if (d.own_in_pass && !d.need_own) own_sum = own[own_at++];
-        float4 own_tile_sum = make_float4(0, 0, 0, 0);  // need_own: the finished sum of its own tile (k_patch_own)
-        if (d.need_own) own_tile_sum = no_sum[no_at++];
-        // the hits of one destination are in generation order: runs of equal tile, ascending
-        for (size_t a = d.first; a < d.last;) {
-            const int t = fl[hits[a].second].tile;
-            size_t b = a;
-            while (b < d.last && fl[hits[b].second].tile == t) ++b;
-            PatchEntry e;
-            e.film_index = d.film_index;
-            e.tile = t;
-            e.nonplain = false;
-            float rr = 0, gg = 0, bb = 0, ww = 0;
-            auto add = [&](const float4 &v) {
-                rr += v.x * 1.f * 1.f;
-                gg += v.y * 1.f * 1.f;
-                bb += v.z * 1.f * 1.f;
-                ww += 1.f;
-            };
-            if (d.own_in_pass && t == d.tile && d.need_own) {
-                rr = own_tile_sum.x, gg = own_tile_sum.y, bb = own_tile_sum.z, ww = own_tile_sum.w;
-            } else {
-                if (d.own_in_pass && t == d.tile) rr = own_sum.x, gg = own_sum.y, bb = own_sum.z, ww = own_sum.w;
-                for (size_t h = a; h < b; ++h) add(L[size_t(plan->list_of_flag[hits[h].second])]);
-            }
-            for (size_t h = a; h < b; ++h) e.nonplain = e.nonplain || !fl[hits[h].second].plain_k0;
-            e.r = rr, e.g = gg, e.b = bb, e.w = ww;
-            entries->push_back(e);
-            a = b;
-        }
-    }
-    tm.lap("tile sums");
-    return IILE_OK;
-}
-
-// After k_film_resolve: every pixel reached by a sample the resolve kernel does not place is rebuilt from its tiles'
-// exact sums, added in tile index order (Film::MergeFilmTile, film.cpp:135-148).
-int patch_merge(iile_scene *sc, const DScene &S, const PassDesc &Pf, std::vector<PatchEntry> *entries, float4 *film_dev, uint64_t *n_patched,
-                hipStream_t stream) {
-    *n_patched = 0;
-    if (entries->empty()) return IILE_OK;
-    PatchTimer tm;
-    std::sort(entries->begin(), entries->end(), [](const PatchEntry &a, const PatchEntry &b) {
-        return a.film_index != b.film_index ? a.film_index < b.film_index : a.tile < b.tile;
-    });
-    const int fw = S.crop_x1 - S.crop_x0, ntx = Pf.n_tiles_x;
-    struct Group {
-        size_t first, last;
-        int own_tile;        // the pixel's own (owned) tile if no entry covers it, else -1
-        uint32_t own_slot;
-    };
-    std::vector<Group> groups;
-    std::vector<uint32_t> own_idx;
-    for (size_t a = 0; a < entries->size();) {
-        size_t b = a;
-        bool nonplain = false;
-        while (b < entries->size() && (*entries)[b].film_index == (*entries)[a].film_index) {
-            if ((*entries)[b].nonplain) nonplain = true;
-            ++b;
-        }
-        if (nonplain) {
-            Group g{a, b, -1, 0u};
-            const uint32_t fi = (*entries)[a].film_index;
-            const int qx = S.crop_x0 + int(fi % uint32_t(fw)), qy = S.crop_y0 + int(fi / uint32_t(fw));
-            if (qx >= S.samp_x0 && qx < S.samp_x1 && qy >= S.samp_y0 && qy < S.samp_y1) {
-                const int tx = (qx - S.samp_x0) / 16, ty = (qy - S.samp_y0) / 16, t = ty * ntx + tx;
-                bool covered = false;
-                for (size_t h = a; h < b; ++h) covered = covered || (*entries)[h].tile == t;
-                if (!covered && sc->slot_of(t) >= 0) {
-                    g.own_tile = t;
-                    g.own_slot = uint32_t(sc->slot_of(t)) * 256u + uint32_t((qy - S.samp_y0 - ty * 16) * 16 + (qx - S.samp_x0 - tx * 16));
-                    own_idx.push_back(g.own_slot);
-                }
-            }
-            groups.push_back(g);
-        }
-        a = b;
-    }
-    if (groups.empty()) return IILE_OK;
-    LaunchCfg cfg{sc->n_cus, stream, false};
-    int rc;
-    std::vector<float4> own(own_idx.size());
-    if (!own_idx.empty()) {
-        if ((rc = scratch_reserve(sc, scratch_bytes<uint32_t>(own_idx.size()) + scratch_bytes<float4>(own.size()), stream))) return rc;
-        uint32_t *di = nullptr;
-        if ((rc = scratch_put(sc, own_idx, stream, &di))) return rc;
-        float4 *dv = scratch_take<float4>(sc, own.size());
-        launch_gather4(sc->fb.tile_rgbw, di, int(own_idx.size()), dv, cfg);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(own.data(), dv, own.size() * sizeof(float4), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    std::vector<uint32_t> out_idx(groups.size());
-    std::vector<float4> out_val(groups.size());
-    size_t own_at = 0;
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group &g = groups[gi];
-        float4 o = make_float4(0, 0, 0, 0);
-        auto add_tile = [&](float rr, float gg, float bb, float ww) {
-            o.x += 0.412453f * rr + 0.357580f * gg + 0.180423f * bb;  // RGBToXYZ, spectrum.h:62-66
-            o.y += 0.212671f * rr + 0.715160f * gg + 0.072169f * bb;
-            o.z += 0.019334f * rr + 0.119193f * gg + 0.950227f * bb;
-            o.w += ww;
-        };
-        bool own_added = g.own_tile < 0;
-        float4 own_sum = make_float4(0, 0, 0, 0);
-        if (g.own_tile >= 0) own_sum = own[own_at++];
-        for (size_t h = g.first; h < g.last; ++h) {
-            const PatchEntry &e = (*entries)[h];
-            if (!own_added && g.own_tile < e.tile) {
-                add_tile(own_sum.x, own_sum.y, own_sum.z, own_sum.w);
-                own_added = true;
-            }
-            add_tile(e.r, e.g, e.b, e.w);
-        }
-        if (!own_added) add_tile(own_sum.x, own_sum.y, own_sum.z, own_sum.w);
-        out_idx[gi] = (*entries)[g.first].film_index;
-        out_val[gi] = o;
-    }
-    {
-        if ((rc = scratch_reserve(sc, scratch_bytes<uint32_t>(out_idx.size()) + scratch_bytes<float4>(out_val.size()), stream))) return rc;
-        uint32_t *di = nullptr;
-        float4 *dv = nullptr;
-        if ((rc = scratch_put(sc, out_idx, stream, &di)) || (rc = scratch_put(sc, out_val, stream, &dv))) return rc;
-        launch_scatter4(film_dev, di, int(out_idx.size()), dv, cfg);
-        HIP_TRY(hipGetLastError());
-        // out_idx / out_val are pageable host vectors that die with this scope: the copies must have been taken
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    tm.lap("merge + scatter");
-    *n_patched = out_idx.size();
-    return IILE_OK;
-}
-}  // namespace
 
 int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw, iile_stats *stats) {
     if (!sc || !prm || !film_xyzw) return fail(IILE_ERR_ARG, "iile_render: null argument");
@@ -1748,12 +1331,8 @@ int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw,
     iile_stats st;
     std::memset(&st, 0, sizeof(st));
     // whole-number film positions are listed for the one-pixel box film (the sample store of wider filters handles them).
-    // Their exact finish runs on the device, on this stream, without a host wait (kernels.hip "exact film finish"); the
-    // host-side version of rounds 1-3 stays behind IILE_DEBUG_HOST_FILM_FINISH as an A/B witness (bench.py refuses to run with it).
-    PatchPlan plan;
-    std::vector<PatchEntry> entries;
-    const bool host_finish = std::getenv("IILE_DEBUG_HOST_FILM_FINISH") != nullptr;
-    if (!S.filter_wide && !host_finish) {
+    // Their exact finish runs on the device, on this stream, without a host wait (kernels.hip "exact film finish").
+    if (!S.filter_wide) {
         rc = ensure_patch(sc, uint64_t(tiles_per_pass) * paths_per_tile, uint64_t(P.n_owned_tiles) * paths_per_tile);
         if (rc) return rc;
         HIP_TRY(hipMemsetAsync(sc->patch.counters, 0, 16, stream));
@@ -1792,20 +1371,11 @@ int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw,
         else
             launch_film_accumulate(S, P, sc->pb, sc->fb, cfg);
         if (timed) HIP_TRY(hipEventRecord(ep->b, stream));
-        if (sc->pb.flag_count && !host_finish) {
+        if (sc->pb.flag_count) {
             // this pass's flagged samples -> exact FilmTile sums (entries) for the pixels they reach
             HIP_TRY(hipMemsetAsync(sc->patch.counters, 0, sizeof(uint32_t), stream));  // hits are per pass; entries add up
             HIP_TRY(hipMemsetAsync(sc->patch.keys, 0xff, patch_table_bytes, stream));
             launch_patch_pass(S, P, sc->pb, sc->fb, sc->patch, cfg);
-        } else if (sc->pb.flag_count) {
-            // the pass's list of whole-number film positions is final after its first k_extend: fetch and sort it on the
-            // host while the GPU works through the rest of the pass, then take the exact tile sums once it is done
-            HIP_TRY(hipStreamWaitEvent(sc->aux_stream, sc->ev_flags, 0));
-            rc = patch_prepare(sc, S, P, sc->aux_stream, &plan);
-            if (rc) return rc;
-            // (its index lists are built on the host while the pass is still running; its gathers queue up behind the pass)
-            rc = patch_pass_finish(sc, S, &plan, &entries, stream);
-            if (rc) return rc;
         }
         st.n_passes++;
         st.n_paths += P.n_paths;
@@ -1824,16 +1394,10 @@ int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw,
     } else {
         launch_film_resolve(S, P, F, cfg);
         HIP_TRY(hipGetLastError());
-        if (!host_finish && sc->pb.flag_count && pix_slots) {
+        if (sc->pb.flag_count && pix_slots) {
             HIP_TRY(hipMemsetAsync(sc->patch.keys, 0xff, patch_table_bytes, stream));
             launch_patch_merge(S, P, F, sc->patch, cfg);
             HIP_TRY(hipGetLastError());
-        }
-        if (!entries.empty()) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            uint64_t n_patched = 0;
-            rc = patch_merge(sc, S, P, &entries, F.film_xyzw, &n_patched, stream);
-            if (rc) return rc;
         }
     }
     sc->pb.flag_count = nullptr;
@@ -1845,7 +1409,7 @@ int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw,
     // The film is complete once the stream drains. Statistics need the drain; a device-resident film without stats
     // stays asynchronous on `stream` past the last pass (the exact film finish waits for each pass on that stream, and
     // only on it: nothing here touches the null stream or synchronises the device).
-    if (!(stats || !prm->film_on_device) && pix_slots && !S.filter_wide && !host_finish) {
+    if (!(stats || !prm->film_on_device) && pix_slots && !S.filter_wide) {
         sc->overflow_unchecked = true;   // nobody waits here: iile_render_status / the next iile_render reads the error word
         sc->overflow_stream = stream;
     }
@@ -1858,7 +1422,7 @@ int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw,
             rc = collect_times(sc, &st);
             if (rc) return rc;
         }
-        if (pix_slots && !S.filter_wide && !host_finish) {  // did the exact film finish run out of room? (checked wherever the host waits anyway)
+        if (pix_slots && !S.filter_wide) {  // did the exact film finish run out of room? (checked wherever the host waits anyway)
             uint32_t pc[4] = {0, 0, 0, 0};
             HIP_TRY(hipMemcpyAsync(pc, sc->patch.counters, sizeof(pc), hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));

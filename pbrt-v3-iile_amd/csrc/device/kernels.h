@@ -212,10 +212,6 @@ void launch_trig_probe(int n, const float *x, float *out, const LaunchCfg &cfg);
 // one pass's flagged samples -> entries (after the pass's k_film_accumulate); all entries -> film (after k_film_resolve)
 void launch_patch_pass(const DScene &S, const PassDesc &P, const PassBuffers &B, const FilmBuffers &F, const PatchDev &D, const LaunchCfg &cfg);
 void launch_patch_merge(const DScene &S, const PassDesc &P, const FilmBuffers &F, const PatchDev &D, const LaunchCfg &cfg);
-void launch_patch_own(const DScene &S, const float4 *L, int n, const uint32_t *local_slot, const uint32_t *range3, const uint32_t *flag_pid,
-                      int kc, float4 *out, const LaunchCfg &cfg);
-void launch_gather4(const float4 *src, const uint32_t *idx, int n, float4 *out, const LaunchCfg &cfg);
-void launch_scatter4(float4 *dst, const uint32_t *idx, int n, const float4 *in, const LaunchCfg &cfg);
 void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, const float *pdp, float *out,
                           const LaunchCfg &cfg);
 constexpr int kShapeHitFloats = 28;  // = IILE_SHAPE_HIT_FLOATS

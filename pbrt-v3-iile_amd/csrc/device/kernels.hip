@@ -631,39 +631,13 @@ void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, cons
                           const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_texture_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, tex, uv, duv, pdp, out);
 }
-__global__ void k_gather4(const float4 *src, const uint32_t *idx, int n, float4 *out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = src[idx[i]];
-}
-__global__ void k_scatter4(float4 *dst, const uint32_t *idx, int n, const float4 *in) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[idx[i]] = in[i];
-}
-// One exact FilmTile sum per thread for a pixel that receives flagged samples from pixels generated before it in its
-// own tile: those samples first, then its own kc samples, then the flagged samples of later pixels — all in generation
-// order, guarded like k_film_accumulate (see patch_pass_finish in api.hip).
-__global__ void k_patch_own(DScene S, const float4 *L, int n, const uint32_t *local_slot, const uint32_t *range3, const uint32_t *flag_pid,
-                            int kc, float4 *out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float r = 0, g = 0, b = 0, w = 0;
-    auto add = [&](float4 v) {
-        const F3 c = guard_radiance(S, F3{v.x, v.y, v.z});
-        r += c.x * 1.f * 1.f;
-        g += c.y * 1.f * 1.f;
-        b += c.z * 1.f * 1.f;
-        w += 1.f;
-    };
-    const uint32_t b0 = range3[3 * i], b1 = range3[3 * i + 1], b2 = range3[3 * i + 2];
-    for (uint32_t h = b0; h < b1; ++h) add(L[flag_pid[h]]);
-    const uint32_t first = local_slot[i] * uint32_t(kc);
-    for (int k = 0; k < kc; ++k) add(L[first + uint32_t(k)]);
-    for (uint32_t h = b1; h < b2; ++h) add(L[flag_pid[h]]);
-    out[i] = make_float4(r, g, b, w);
-}
 // ---------------------------------------------------------------------------
-// Exact film finish on the device. What patch_prepare / patch_pass_finish / patch_merge of api.hip do with the host in the
-// loop (kept behind IILE_DEBUG_HOST_FILM_FINISH as the A/B witness), as four small kernels that never leave the stream:
+// Exact film finish on the device, for the one-pixel box film. k_film_accumulate / k_film_resolve give every pixel the sum
+// of its own samples (plus the k = 0 zero-offset splats): all there is unless a sample's film position is a whole number,
+// when FilmTile::AddSample (film.h:159-188) also adds it to a neighbouring pixel, in sample order inside its tile. The
+// generation code lists those samples (rare: ~1e-4 of them where pixel coordinates pass 1024); every pixel they touch is
+// recomputed the way the reference sums it, per contributing tile and tiles in index order, by four small kernels that never
+// leave the stream:
 //   k_patch_hits    every flagged sample (kcommon.h flag_whole_film_position) -> one hit record per OTHER pixel it lands in
 //                   (FilmTile::AddSample's support, film.h:159-166, clipped to its tile's FilmTile bounds, film.cpp:92-103),
 //                   linked into the list of its destination through a hash table over film indices
@@ -672,7 +646,8 @@ __global__ void k_patch_own(DScene S, const float4 *L, int n, const uint32_t *lo
 //                   and forms, per contributing tile, the exact FilmTile sum for that pixel -> an entry
 //   k_patch_index / k_patch_merge   after k_film_resolve: per film pixel with an entry that the resolve kernel cannot have
 //                   placed, the tiles' sums (and the pixel's own tile sum if no entry covers it) converted to XYZ and added
-//                   in tile index order (Film::MergeFilmTile, film.cpp:135-148)
+//                   in tile index order (Film::MergeFilmTile, film.cpp:135-148: the reference merges tiles in completion
+//                   order, the oracle and this in index order, so that the sum does not depend on scheduling)
 // Lists are short (a sample lands in at most three other pixels, a pixel is reached by a handful): they are walked by repeated
 // selection of the next key instead of being sorted, which needs no bound on their length.
 namespace {
@@ -922,16 +897,6 @@ void launch_patch_merge(const DScene &S, const PassDesc &P, const FilmBuffers &F
     hipLaunchKernelGGL(k_patch_merge, dim3(128), dim3(kBlock), 0, cfg.stream, S, P, F, D);
 }
 
-void launch_patch_own(const DScene &S, const float4 *L, int n, const uint32_t *local_slot, const uint32_t *range3, const uint32_t *flag_pid,
-                      int kc, float4 *out, const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_patch_own, dim3((n + 63) / 64), dim3(64), 0, cfg.stream, S, L, n, local_slot, range3, flag_pid, kc, out);
-}
-void launch_gather4(const float4 *src, const uint32_t *idx, int n, float4 *out, const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_gather4, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, src, idx, n, out);
-}
-void launch_scatter4(float4 *dst, const uint32_t *idx, int n, const float4 *in, const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_scatter4, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, dst, idx, n, in);
-}
 void launch_trig_probe(int n, const float *x, float *out, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_trig_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, n, x, out);
 }

@@ -8,7 +8,7 @@ rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 gen = [i for i, r in enumerate(rows) if "k_extend<false" in r["Kernel_Name"] and r["Kernel_Name"].split("(")[0].rstrip().endswith("true>")]
 i0 = gen[-1]
 # the frame ends with the last film kernel after i0
-last = max(i for i, r in enumerate(rows) if i >= i0 and ("k_film" in r["Kernel_Name"] or "k_scatter4" in r["Kernel_Name"] or "k_gather4" in r["Kernel_Name"]))
+last = max(i for i, r in enumerate(rows) if i >= i0 and ("k_film" in r["Kernel_Name"] or "k_patch" in r["Kernel_Name"]))
 iv = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows[i0:last + 1])
 t0, end = iv[0][0], iv[0][1]
 gaps = []
