@@ -302,6 +302,9 @@ int iile_bvh_pack_probe(int32_t n_nodes, const iile_bvh_node *nodes, int32_t n_i
 /* How this build packs the refs of a four-wide record: 0 = the plain ref and an axes word of its own; 2 = ref << 2 | split
  * axis (of the node, its first child, its second child) — one vector load less per interior step. */
 int32_t iile_wide_ref_shift(void);
+/* Light::Sample_Li of delta light `light` (point, spot, distant, projection, goniometric: iile_light_is_delta; any other is
+ * IILE_ERR_ARG) at n points p3, each an Interaction without a surface: out7 = {wi.xyz, Li.rgb, pdf} per point. */
+int iile_light_sample_li(iile_scene *scene, int32_t light, int32_t n, const float *p3, float *out7);
 /* ImageTexture<RGBSpectrum, Spectrum>::Evaluate (src/textures/imagemap.h:87-94) of image texture `tex` at n
  * surface points given by (u, v) and the screen-space differentials {du/dx, dv/dx, du/dy, dv/dy}. */
 int iile_texture_eval(iile_scene *scene, int32_t tex, int32_t n, const float *uv2, const float *duv4, float *rgb3);

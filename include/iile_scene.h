@@ -181,7 +181,8 @@ enum { IILE_AA_CLOSEDFORM = 0, IILE_AA_NONE = 1 };
 
 /* A light: DiffuseAreaLight on a shape (src/lights/diffuse.h:48-75) or one of the delta lights
  * PointLight (src/lights/point.h:49-70), SpotLight (src/lights/spot.h:49-74), DistantLight
- * (src/lights/distant.h:49-72). */
+ * (src/lights/distant.h:49-72), ProjectionLight (src/lights/projection.h:49-76), GonioPhotometricLight
+ * (src/lights/goniometric.h:52-91). */
 #define IILE_MAX_LIGHTS 8 /* the device keeps per-voxel light distributions for this many */
 #define IILE_LIGHT_DIFFUSE_AREA 0
 #define IILE_LIGHT_POINT 1
@@ -190,6 +191,14 @@ enum { IILE_AA_CLOSEDFORM = 0, IILE_AA_NONE = 1 };
 #define IILE_LIGHT_AREA_TRIANGLE 4 /* DiffuseAreaLight on one triangle (every triangle of an emitting mesh is a light) */
 #define IILE_LIGHT_INFINITE 5      /* InfiniteAreaLight without an environment map (src/lights/infinite.h:51-84) */
 #define IILE_LIGHT_AREA_QUADRIC 6  /* DiffuseAreaLight on a disk or a cylinder: `prim` is its primitive, `sphere` is -1 */
+#define IILE_LIGHT_PROJECTION 7    /* ProjectionLight: a point light whose intensity is an image projected through a frustum */
+#define IILE_LIGHT_GONIOMETRIC 8   /* GonioPhotometricLight: a point light whose intensity is an image over the sphere of directions */
+/* LightFlags::DeltaPosition | DeltaDirection (IsDeltaLight, src/core/light.h:54-57): sampled by Sample_Li alone with pdf 1, never
+ * found by a ray. The one list of them: the host, libiile_gpu.so's refusal pass and its kernels all ask here. */
+IILE_INLINE int iile_light_is_delta(int32_t type) {
+    return type == IILE_LIGHT_POINT || type == IILE_LIGHT_SPOT || type == IILE_LIGHT_DISTANT || type == IILE_LIGHT_PROJECTION ||
+           type == IILE_LIGHT_GONIOMETRIC;
+}
 typedef struct iile_light {
     float lemit[3];  /* area: Lemit (L * scale); point, spot: I * scale; distant: L * scale */
     int32_t two_sided;
@@ -217,7 +226,16 @@ typedef struct iile_light {
      * then the marginal one {func[h], cdf[h + 1], funcInt} over the rows' funcInt */
     int32_t dist_w, dist_h;
     int64_t dist_offset;
+    /* projection and goniometric lights add no member (sizeof(iile_light) stays 152). Both: pos = pLight, lemit = I * scale, w2l as
+     * for the spot light, and env_tex = the pyramid of "mapname" among the textures (the image's texels as read, not times I, not
+     * flipped in y; MIPMap's defaults: repeat wrap), or -1 without a map or when it cannot be read (the reference's null
+     * projectionMap / mipmap: Projection() is 1 inside the frustum, Scale() is 1). The projection light (ctor, projection.cpp:45-75)
+     * keeps cosTotalWidth = 1 / h (:70-74) in cos_total_width and, in l2w (a LightToWorld it never uses), the IILE_PROJ_* values */
 } iile_light;
+/* iile_light::l2w[] of a projection light: the terms of lightProjection = Perspective(fov, hither, yon) (transform.cpp:303-311)
+ * that Projection() uses — m[0][0] and m[1][1]; row 3 is {0, 0, 1, 0} and every other entry of rows 0, 1 and 3 is 0 — then hither
+ * (1e-3), "fov" as given (45), and screenBounds {pMin.x, pMin.y, pMax.x, pMax.y} in [IILE_PROJ_BOUNDS .. + 3]; l2w[8] is 0 */
+enum { IILE_PROJ_M00 = 0, IILE_PROJ_M11 = 1, IILE_PROJ_HITHER = 2, IILE_PROJ_FOV = 3, IILE_PROJ_BOUNDS = 4 };
 
 /* PerspectiveCamera (src/cameras/perspective.cpp:50-72, src/core/camera.h:90-111). */
 typedef struct iile_camera {

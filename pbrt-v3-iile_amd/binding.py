@@ -64,6 +64,17 @@ class Light(ctypes.Structure):
                 ("cos_total_width", c_f32), ("cos_falloff_start", c_f32), ("world_radius", c_f32), ("prim", c_i32), ("n_samples", c_i32),
                 ("l2w", c_f32 * 9), ("env_tex", c_i32), ("dist_w", c_i32), ("dist_h", c_i32), ("dist_offset", ctypes.c_int64)]
 
+    def projection(self):
+        """What a projection light keeps in l2w (IILE_PROJ_*, include/iile_scene.h): m[0][0] and m[1][1] of lightProjection, hither,
+        fov and screenBounds {pMin.x, pMin.y, pMax.x, pMax.y}."""
+        v = list(self.l2w)
+        return {"m00": v[0], "m11": v[1], "hither": v[2], "fov": v[3], "screen_bounds": v[4:8]}
+
+
+# iile_light::type
+(LIGHT_DIFFUSE_AREA, LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT, LIGHT_AREA_TRIANGLE, LIGHT_INFINITE, LIGHT_AREA_QUADRIC, LIGHT_PROJECTION,
+ LIGHT_GONIOMETRIC) = range(9)
+
 
 class RenderParams(ctypes.Structure):
     _fields_ = [("k_begin", c_i32), ("k_end", c_i32), ("tile_rank", c_i32), ("tile_nranks", c_i32),
@@ -164,7 +175,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
-               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_render_probes",
+               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_render_probes",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
                "iile_iispt_film_add", "iile_iispt_film_merge",
@@ -280,6 +291,7 @@ def gpu_lib():
         lib.iile_li_samples.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         lib.iile_bsdf_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_texture_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
+        lib.iile_light_sample_li.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp]
         lib.iile_texture_eval_p.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_render_probes.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, ctypes.POINTER(GpuStats), c_vp]
         lib.iile_bsdf_sample.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
@@ -669,6 +681,14 @@ class GpuScene:
         out = np.empty((len(wo), 4), np.float32)
         self._check(gpu_lib().iile_bsdf_eval(self._s, len(wo), mat, wo.ctypes.data, wi.ctypes.data, out.ctypes.data),
                     "iile_bsdf_eval")
+        return out
+
+    def light_sample_li(self, light, p):
+        """Light::Sample_Li of delta light `light` (point, spot, distant, projection, goniometric) at the (n, 3) points p, with no
+        surface in between: (n, 7) {wi.xyz, Li.rgb, pdf}."""
+        p = _f32(p).reshape(-1, 3)
+        out = np.empty((len(p), 7), np.float32)
+        self._check(gpu_lib().iile_light_sample_li(self._s, int(light), len(p), p.ctypes.data, out.ctypes.data), "iile_light_sample_li")
         return out
 
     def render_probes(self, pos, direction, hemi=None, device_out=None, stream=None):

@@ -68,6 +68,7 @@ struct iile_scene {
     int max_depth = 5;
     int spp = 1;
     int light_samples[8] = {1, 1, 1, 1, 1, 1, 1, 1};  // Light::nSamples (iile_light::n_samples), the direct pass's nLightSamples
+    std::vector<int> light_types;                     // iile_light::type of every light (iile_light_sample_li checks it)
     // wavefront workspace, grown on demand and kept across renders
     uint32_t ws_paths = 0;
     uint64_t ws_bytes = 0;
@@ -578,8 +579,7 @@ int check_scene_desc(const iile_scene_desc &d) {
         } else if (l.type == IILE_LIGHT_AREA_QUADRIC) {
             if (l.prim < 0 || l.prim >= d.n_prims || !(d.prim_flags[l.prim] & IILE_PRIM_QUADRIC) || d.prim_light[l.prim] != i)
                 return fail(IILE_ERR_ARG, "quadric area light without its quadric");
-        } else if (l.type != IILE_LIGHT_POINT && l.type != IILE_LIGHT_SPOT && l.type != IILE_LIGHT_DISTANT &&
-                   l.type != IILE_LIGHT_INFINITE) {
+        } else if (!iile_light_is_delta(l.type) && l.type != IILE_LIGHT_INFINITE) {
             return fail(IILE_ERR_UNSUPPORTED, "unsupported light type");
         }
     }
@@ -638,6 +638,10 @@ int check_scene_desc(const iile_scene_desc &d) {
             (il.env_tex < 0 || il.env_tex >= d.n_textures || d.textures[il.env_tex].kind != IILE_TEX_IMAGE || il.dist_w < 1 || il.dist_h < 1 ||
              il.dist_offset < 0 || il.dist_offset + int64_t(2 * il.dist_w + 2) * il.dist_h + 2 * il.dist_h + 2 > d.n_env_dist))
             return fail(IILE_ERR_ARG, "infinite light: bad environment map / distribution reference");
+        // (the lookups of delta_light_li and of the light probe rely on this)
+        if ((il.type == IILE_LIGHT_PROJECTION || il.type == IILE_LIGHT_GONIOMETRIC) && il.env_tex != -1 &&
+            (il.env_tex < 0 || il.env_tex >= d.n_textures || d.textures[il.env_tex].kind != IILE_TEX_IMAGE))
+            return fail(IILE_ERR_ARG, "projection / goniometric light: its map is not an image texture of the scene");
     }
     const iile_sobol &sb = d.sobol;
     if (sb.enabled && (sb.n_dims < need_dims || sb.n_dims > 256 || !sb.matrices32 || sb.log2_resolution < 1 || sb.log2_resolution > 16 ||
@@ -925,6 +929,7 @@ int build_lights(iile_scene *sc, const iile_scene_desc &d) {
     DScene &S = sc->ds;
     S.n_lights = d.n_lights;
     for (int i = 0; i < d.n_lights && i < 8; ++i) sc->light_samples[i] = std::max(1, int(d.lights[i].n_samples));
+    for (int i = 0; i < d.n_lights; ++i) sc->light_types.push_back(d.lights[i].type);
     std::vector<DLight> lts(d.n_lights);
     for (int i = 0; i < d.n_lights; ++i) {
         const iile_light &l = d.lights[i];
@@ -1211,7 +1216,8 @@ int iile_device_zero(void *dev, uint64_t bytes, void *stream) {
 static_assert(kLightDiffuseArea == IILE_LIGHT_DIFFUSE_AREA && kLightPoint == IILE_LIGHT_POINT &&
                   kLightSpot == IILE_LIGHT_SPOT && kLightDistant == IILE_LIGHT_DISTANT &&
                   kLightAreaTriangle == IILE_LIGHT_AREA_TRIANGLE && kLightInfinite == IILE_LIGHT_INFINITE &&
-                  kLightAreaQuadric == IILE_LIGHT_AREA_QUADRIC,
+                  kLightAreaQuadric == IILE_LIGHT_AREA_QUADRIC && kLightProjection == IILE_LIGHT_PROJECTION &&
+                  kLightGoniometric == IILE_LIGHT_GONIOMETRIC,
               "light type codes");
 static_assert(kQuadricDisk == IILE_QUADRIC_DISK && kQuadricCylinder == IILE_QUADRIC_CYLINDER && kMaxQuadrics == IILE_MAX_QUADRICS,
               "quadric kind codes");
@@ -2272,6 +2278,20 @@ int iile_bsdf_eval_ng(iile_scene *sc, int32_t n, int32_t mat, const float *ng3, 
 int iile_bsdf_sample_ng(iile_scene *sc, int32_t n, int32_t mat, const float *ng3, const float *wo3, const float *u2, float *out7) {
     if (!ng3) return fail(IILE_ERR_ARG, "iile_bsdf_sample_ng: null normal");
     return bsdf_probe(sc, n, mat, wo3, u2, 2, 1, out7, 7, ng3);
+}
+
+int iile_light_sample_li(iile_scene *sc, int32_t light, int32_t n, const float *p3, float *out7) {
+    if (!sc || n < 0 || !p3 || !out7 || light < 0 || light >= sc->ds.n_lights)
+        return fail(IILE_ERR_ARG, "iile_light_sample_li: bad argument");
+    if (!iile_light_is_delta(sc->light_types[size_t(light)])) return fail(IILE_ERR_ARG, "iile_light_sample_li: not a delta light");
+    DevBuf<float> dp, dout;
+    int rc;
+    if ((rc = dp.put(p3, 3 * size_t(n))) || (rc = dout.alloc(7 * size_t(n)))) return rc;
+    LaunchCfg cfg{sc->n_cus, nullptr, false};
+    if (n) launch_light_probe(sc->ds, n, light, dp.p, dout.p, cfg);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return dout.get(out7, 7 * size_t(n));
 }
 
 int iile_texture_eval(iile_scene *sc, int32_t tex, int32_t n, const float *uv2, const float *duv4, float *rgb3) {

@@ -2694,9 +2694,43 @@ DEV float power_heuristic(float fpdf, float gpdf) {  // sampling.h:169-172 with 
 DEV F3 area_light_L(const DLight &lt, F3 n, F3 w) {
     return (lt.two_sided || dot(n, w) > 0) ? F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]} : F3{0, 0, 0};
 }
-// Sample_Li of a delta light at p: PointLight (lights/point.cpp:43-52), SpotLight with its Falloff (spot.cpp:53-76),
-// DistantLight (distant.cpp:50-61). The pdf is 1; *target is the light-side end of the shadow ray.
-DEV F3 delta_light_li(const DLight &lt, F3 p, F3 *wi, F3 *target) {
+// ProjectionLight::Projection(w) (lights/projection.cpp:88-99); the map is projectionMap, a pyramid among the textures, or none
+DEV F3 projection_light_projection(const DScene &S, const DLight &lt, F3 w) {
+    const F3 wl = inf_w2l(lt, w);  // WorldToLight(w) on a vector, transform.h:236-241
+    if (wl.z < lt.l2w[IILE_PROJ_HITHER]) return F3{0, 0, 0};  // :91
+    // lightProjection(Point3f(wl.x, wl.y, wl.z)): Transform::operator()(Point3f), transform.h:222-233, with Point3 / wp as a
+    // multiplication by 1 / wp (geometry.h:499-503). Perspective()'s rows 0, 1 and 3 are {m00, 0, 0, 0}, {0, m11, 0, 0} and
+    // {0, 0, 1, 0} (transform.cpp:303-311): the products with their exact zeros add +-0 to a finite sum and are left out, the
+    // values are the reference's (wl is finite; wp = 1 * wl.z >= hither)
+    float xp = lt.l2w[IILE_PROJ_M00] * wl.x;
+    float yp = lt.l2w[IILE_PROJ_M11] * wl.y;
+    const float wp = wl.z;
+    if (wp != 1) {
+        const float inv = 1.f / wp;
+        xp = inv * xp;
+        yp = inv * yp;
+    }
+    const float *sb = lt.l2w + IILE_PROJ_BOUNDS;
+    const float x0 = sb[0], y0 = sb[1], x1 = sb[2], y1 = sb[3];
+    if (!(xp >= x0 && xp <= x1 && yp >= y0 && yp <= y1)) return F3{0, 0, 0};  // Inside(Point2f, Bounds2f), geometry.h:1370-1373
+    if (lt.env_tex < 0) return F3{1, 1, 1};                                    // :96
+    float ox = xp - x0, oy = yp - y0;  // screenBounds.Offset, geometry.h:729-734
+    if (x1 > x0) ox /= x1 - x0;
+    if (y1 > y0) oy /= y1 - y0;
+    return inf_lookup(S, lt, ox, oy);  // projectionMap->Lookup(st), :98
+}
+// GonioPhotometricLight::Scale(w) (lights/goniometric.h:69-77)
+DEV F3 goniometric_light_scale(const DScene &S, const DLight &lt, F3 w) {
+    if (lt.env_tex < 0) return F3{1, 1, 1};  // !mipmap, :75
+    const F3 wl = normalize(inf_w2l(lt, w));  // Normalize(WorldToLight(w))
+    const F3 wp = F3{wl.x, wl.z, wl.y};       // std::swap(wp.y, wp.z)
+    const float theta = spherical_theta(wp), phi = spherical_phi(wp);
+    return inf_lookup(S, lt, phi * kInv2Pi, theta * kInvPi);  // mipmap->Lookup(Point2f(phi * Inv2Pi, theta * InvPi))
+}
+// Sample_Li of a delta light (iile_light_is_delta) at p: PointLight (lights/point.cpp:43-52), SpotLight with its Falloff
+// (spot.cpp:53-76), DistantLight (distant.cpp:50-61), ProjectionLight (projection.cpp:77-86), GonioPhotometricLight
+// (goniometric.cpp:43-53). The pdf is 1; *target is the light-side end of the shadow ray.
+DEV F3 delta_light_li(const DScene &S, const DLight &lt, F3 p, F3 *wi, F3 *target) {
     const F3 pos = F3{lt.pos[0], lt.pos[1], lt.pos[2]};
     const F3 I = F3{lt.lemit[0], lt.lemit[1], lt.lemit[2]};
     if (lt.type == kLightDistant) {
@@ -2706,7 +2740,9 @@ DEV F3 delta_light_li(const DLight &lt, F3 p, F3 *wi, F3 *target) {
     }
     *wi = normalize(pos - p);
     *target = pos;  // pLight
-    if (lt.type != kLightSpot) return sdiv(I, length_sq(pos - p));
+    if (lt.type == kLightPoint) return sdiv(I, length_sq(pos - p));
+    if (lt.type == kLightProjection) return sdiv(I * projection_light_projection(S, lt, -*wi), length_sq(pos - p));
+    if (lt.type == kLightGoniometric) return sdiv(I * goniometric_light_scale(S, lt, -*wi), length_sq(pos - p));
     const F3 w = -*wi;
     const F3 wl = normalize(F3{lt.w2l[0] * w.x + lt.w2l[1] * w.y + lt.w2l[2] * w.z,
                                lt.w2l[3] * w.x + lt.w2l[4] * w.y + lt.w2l[5] * w.z,
@@ -2765,10 +2801,10 @@ DEV uint32_t estimate_direct_request(const DScene &S, const DLight &lt, const DS
                 nee_flags |= NEE_HAS_MIS;
             }
         }
-    } else if (EXT && lt.type != kLightDiffuseArea && lt.type != kLightAreaTriangle && lt.type != kLightAreaQuadric) {
+    } else if (EXT && iile_light_is_delta(lt.type)) {
         // a delta light (integrator.cpp:150-166): light sample only, weight 1
         F3 wi, target;
-        const F3 Li = delta_light_li(lt, is.p, &wi, &target);
+        const F3 Li = delta_light_li(S, lt, is.p, &wi, &target);
         if (!is_black(Li)) {
             const F3 f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, is.sn);
             if (!is_black(f)) {

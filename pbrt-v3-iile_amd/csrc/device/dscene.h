@@ -12,6 +12,7 @@
 //  * Ray / hit / NEE queues are arrays of float4 records so that a wavefront's
 //    64 lanes issue full-width 16-byte coalesced loads and stores.
 #pragma once
+#include "../../../include/iile_scene.h"
 #include "dmath.h"
 
 namespace iile {
@@ -77,7 +78,7 @@ enum { kTexImage = 0, kTexScale = 1, kTexMix = 2, kTexChecker2D = 3, kTexChecker
 enum { kMapUV = 0, kMapSpherical = 1, kMapCylindrical = 2, kMapPlanar = 3 };                                          // = IILE_MAP_*
 enum { kAAClosedForm = 0, kAANone = 1 };                                                                               // = IILE_AA_*
 enum { kLightDiffuseArea = 0, kLightPoint = 1, kLightSpot = 2, kLightDistant = 3, kLightAreaTriangle = 4,
-       kLightInfinite = 5, kLightAreaQuadric = 6 };  // = IILE_LIGHT_* (checked in api.hip)
+       kLightInfinite = 5, kLightAreaQuadric = 6, kLightProjection = 7, kLightGoniometric = 8 };  // = IILE_LIGHT_* (checked in api.hip)
 struct DLight {
     float lemit[3];  // area: Lemit; point: I
     int two_sided;
@@ -93,6 +94,8 @@ struct DLight {
     int dist_w, dist_h;     // infinite: size of the Distribution2D
     long long dist_offset;  // its tables in DScene::env_dist
     int quadric;            // area light on a disk or a cylinder (kLightAreaQuadric): its index in DScene::quadrics; else -1
+    // (the projection and goniometric lights keep pLight in pos, WorldToLight in w2l and their map in env_tex, -1: none; the
+    //  projection light its IILE_PROJ_* values in l2w)
 };
 // Per Halton dimension: base, float reciprocal and offset of its digit permutation.
 // The digits are peeled in double arithmetic (exact for any u32 index, see

@@ -212,6 +212,7 @@ void launch_trig_probe(int n, const float *x, float *out, const LaunchCfg &cfg);
 // one pass's flagged samples -> entries (after the pass's k_film_accumulate); all entries -> film (after k_film_resolve)
 void launch_patch_pass(const DScene &S, const PassDesc &P, const PassBuffers &B, const FilmBuffers &F, const PatchDev &D, const LaunchCfg &cfg);
 void launch_patch_merge(const DScene &S, const PassDesc &P, const FilmBuffers &F, const PatchDev &D, const LaunchCfg &cfg);
+void launch_light_probe(const DScene &S, int n, int light, const float *p, float *out, const LaunchCfg &cfg);
 void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, const float *pdp, float *out,
                           const LaunchCfg &cfg);
 constexpr int kShapeHitFloats = 28;  // = IILE_SHAPE_HIT_FLOATS

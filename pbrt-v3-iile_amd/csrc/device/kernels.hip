@@ -627,6 +627,21 @@ __global__ void k_shape_hit_probe(DScene S, int n, const float *o, const float *
 void launch_shape_hit_probe(const DScene &S, int n, const float *o, const float *d, const int *prim, float *out, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_shape_hit_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, o, d, prim, out);
 }
+// Light::Sample_Li of delta light `light` at point i (an Interaction without normal or error bounds): {wi, Li, pdf} (test probe;
+// the caller checked that the light is a delta light, iile_scene_create that its map is a texture of the scene)
+__global__ void k_light_probe(DScene S, int n, int light, const float *p, float *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    F3 wi, target;
+    const F3 Li = delta_light_li(S, S.lights[light], F3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}, &wi, &target);
+    float *r = out + 7 * size_t(i);
+    r[0] = wi.x, r[1] = wi.y, r[2] = wi.z;
+    r[3] = Li.x, r[4] = Li.y, r[5] = Li.z;
+    r[6] = 1.f;
+}
+void launch_light_probe(const DScene &S, int n, int light, const float *p, float *out, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_light_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, light, p, out);
+}
 void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, const float *pdp, float *out,
                           const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_texture_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, tex, uv, duv, pdp, out);

@@ -18,9 +18,9 @@ DEV F3 sample_li_plain(const DScene &S, const DLight &lt, F3 po, float u0, float
         F3 wi, target;
         return inf_sample_li(S, lt, po, u0, u1, &wi, pdf, &target);
     }
-    if (lt.type == kLightPoint || lt.type == kLightSpot || lt.type == kLightDistant) {
+    if (iile_light_is_delta(lt.type)) {
         F3 wi, target;
-        return delta_light_li(lt, po, &wi, &target);
+        return delta_light_li(S, lt, po, &wi, &target);
     }
     Isect ref;  // DiffuseAreaLight::Sample_Li, lights/diffuse.cpp:68-81
     ref.p = po;

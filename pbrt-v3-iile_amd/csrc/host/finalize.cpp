@@ -356,6 +356,13 @@ bool finalize_scene(HostScene *s, std::string *err) {
             case IILE_LIGHT_POINT: pw[c] = 4 * kPi * L; break;  // point.cpp:55
             case IILE_LIGHT_SPOT: pw[c] = L * 2 * kPi * (1 - .5f * (lt.cos_falloff_start + lt.cos_total_width)); break;  // spot.cpp:75-77
             case IILE_LIGHT_DISTANT: pw[c] = L * kPi * wr * wr; break;  // distant.cpp:61-63
+            case IILE_LIGHT_PROJECTION:     // projection.cpp:101-107: (projectionMap->Lookup((.5, .5), .5) or 1) * I * 2 Pi (1 - cosTotalWidth)
+            case IILE_LIGHT_GONIOMETRIC: {  // goniometric.cpp:55-59: 4 Pi * I * (mipmap->Lookup((.5, .5), .5) or 1)
+                float rgb[3] = {1.f, 1.f, 1.f};
+                if (lt.env_tex >= 0) mip_lookup_width(s->textures[size_t(lt.env_tex)], .5f, .5f, .5f, rgb);
+                pw[c] = lt.type == IILE_LIGHT_PROJECTION ? rgb[c] * L * 2 * kPi * (1.f - lt.cos_total_width) : 4 * kPi * L * rgb[c];
+                break;
+            }
             default: {  // infinite.cpp:86-90: Pi r^2 * Lmap->Lookup((.5, .5), .5)
                 float rgb[3];
                 mip_lookup_width(s->textures[size_t(lt.env_tex)], .5f, .5f, .5f, rgb);

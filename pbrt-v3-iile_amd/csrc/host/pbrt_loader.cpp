@@ -515,8 +515,10 @@ class Loader {
             gs_.has_area_light = true;
             gs_.area_light_params = ps;
         } else if (d == "LightSource") {  // api.cpp:1344-1358 (pbrtLightSource), MakeLight api.cpp:770-806
-            if (name != "point" && name != "spot" && name != "distant" && name != "infinite" && name != "exinfinite")
-                return fail("LightSource \"" + name + "\" is not supported (point, spot, distant, infinite; area lights)");
+            if (name != "point" && name != "spot" && name != "distant" && name != "infinite" && name != "exinfinite" &&
+                name != "projection" && name != "goniometric")
+                return fail("LightSource \"" + name +
+                            "\" is not supported (point, spot, distant, infinite, exinfinite, projection, goniometric; area lights)");
             float I[3] = {1, 1, 1}, sc[3] = {1, 1, 1};
             ps.rgb((name == "distant" || name == "infinite" || name == "exinfinite") ? "L" : "I", I);
             ps.rgb("scale", sc);
@@ -600,6 +602,51 @@ class Loader {
                 scene_->textures.push_back(std::move(ht));
                 lt.env_tex = int(scene_->textures.size()) - 1;
                 // world_radius is set once the scene bounds are known (finalize_scene)
+            } else if (name == "projection" || name == "goniometric") {
+                // CreateProjectionLight (lights/projection.cpp:134-143) and its ctor (:45-75); CreateGoniometricLight
+                // (lights/goniometric.cpp:86-94) and its ctor (goniometric.h:57-68): the CTM is LightToWorld
+                const V3 pl = ctm_.point(V3(0, 0, 0));
+                lt.type = name == "projection" ? IILE_LIGHT_PROJECTION : IILE_LIGHT_GONIOMETRIC;
+                lt.pos[0] = pl.x;
+                lt.pos[1] = pl.y;
+                lt.pos[2] = pl.z;
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 3; ++c) lt.w2l[3 * r + c] = ctm_.inv.m[r][c];  // WorldToLight = Inverse(LightToWorld)
+                // the map as ReadImage returns it (not times I, not flipped), under MIPMap<RGBSpectrum>(resolution, texels)'s
+                // defaults; a name that cannot be read is the reference's null map (a warning, no failure)
+                lt.env_tex = -1;
+                int w = 0, h = 0;
+                std::string mapname = ps.one_string("mapname", "");
+                if (!mapname.empty()) {
+                    if (mapname[0] != '/') mapname = search_dir_ + "/" + mapname;
+                    std::vector<float> rgb;
+                    std::string why;
+                    if (read_image(mapname, &rgb, &w, &h, &why)) {
+                        HostTexture ht;
+                        std::memset(&ht.t, 0, sizeof(ht.t));  // MIPMap defaults: EWA, maxAniso 8, repeat (mipmap.h:66-67)
+                        ht.t.wrap = IILE_WRAP_REPEAT;
+                        ht.t.max_aniso = 8.f;
+                        ht.t.su = ht.t.sv = 1.f;
+                        if (!build_mip_pyramid(rgb, w, h, &ht, &why)) return fail(name + " light: " + why);
+                        scene_->textures.push_back(std::move(ht));
+                        lt.env_tex = int(scene_->textures.size()) - 1;
+                    } else
+                        std::fprintf(stderr, "Warning: %s\n", why.c_str());
+                }
+                if (name == "projection") {
+                    const float fov = ps.one_float("fov", 45.f), hither = 1e-3f;
+                    const float aspect = lt.env_tex >= 0 ? float(w) / float(h) : 1.f;  // projection.cpp:59-65
+                    const float sb_aspect[4] = {-aspect, -1, aspect, 1}, sb_tall[4] = {-1, -1 / aspect, 1, 1 / aspect};
+                    float *sb = lt.l2w + IILE_PROJ_BOUNDS;
+                    for (int i = 0; i < 4; ++i) sb[i] = aspect > 1 ? sb_aspect[i] : sb_tall[i];
+                    const Xform proj = xf_perspective(fov, hither, 1e30f);  // hither, yon: projection.cpp:66-68
+                    lt.l2w[IILE_PROJ_M00] = proj.m.m[0][0];  // (the rest of rows 0, 1 and 3 is 0, 0, 1, 0: iile_scene.h)
+                    lt.l2w[IILE_PROJ_M11] = proj.m.m[1][1];
+                    lt.l2w[IILE_PROJ_HITHER] = hither;
+                    lt.l2w[IILE_PROJ_FOV] = fov;
+                    const float hh = (sb[0] * sb[0] + sb[1] * sb[1] + 1);
+                    lt.cos_total_width = 1 / hh;  // projection.cpp:70-74
+                }
             } else {  // CreateDistantLight, lights/distant.cpp:94-102; ctor :43-48
                 const V3 w = normalize(ctm_.vector(from - to));
                 lt.type = IILE_LIGHT_DISTANT;
