@@ -149,7 +149,8 @@ int iile_trace_any(iile_scene *scene, int32_t n, const float *o3, const float *d
  * SampleDimension(index, dim0 + d). */
 int iile_halton_samples(iile_scene *scene, int32_t n, const int32_t *px, const int32_t *py, const int32_t *k,
                         int32_t dim0, int32_t ndims, float *out, uint32_t *index_out);
-/* PerspectiveCamera::GenerateRayDifferential (origin / direction only). plens may be NULL. */
+/* PerspectiveCamera::GenerateRayDifferential or, for an environment camera, EnvironmentCamera::GenerateRay (origin /
+ * direction only). plens may be NULL; the environment camera ignores it. */
 int iile_camera_rays(iile_scene *scene, int32_t n, const float *pfilm2, const float *plens2, float *o3, float *d3);
 /* Radiance of n individual camera samples through the full wavefront pipeline,
  * after the NaN / negative / inf guards; nrays (optional): {closest, shadow} per sample. */

@@ -110,6 +110,10 @@ int iile_host_scene_light(const iile_host_scene *scene, int32_t index, iile_ligh
 /* Copies level `level` (level_w x level_h RGB texels, row 0 = bottom scanline) of that texture. */
 int iile_host_scene_texture_level(const iile_host_scene *scene, int32_t index, int32_t level, float *rgb);
 
+/* Copies the camera of a loaded scene (iile_scene_desc::camera) and returns which camera it is, IILE_CAMERA_PERSPECTIVE or
+ * IILE_CAMERA_ENVIRONMENT (iile_camera_kind); -1 on a null argument. (iile_host_scene_info keeps its 15 members.) */
+int iile_host_scene_camera(const iile_host_scene *scene, iile_camera *out);
+
 /* Film::filterTable of the scene's pixel filter (src/core/film.cpp:65-74): 16 x 16 floats; returns whether the
  * filter is wider than the one-pixel box (iile_scene_desc::film_filter_wide). */
 int iile_host_scene_filter_table(const iile_host_scene *scene, float *table256);

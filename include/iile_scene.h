@@ -237,7 +237,17 @@ typedef struct iile_light {
  * (1e-3), "fov" as given (45), and screenBounds {pMin.x, pMin.y, pMax.x, pMax.y} in [IILE_PROJ_BOUNDS .. + 3]; l2w[8] is 0 */
 enum { IILE_PROJ_M00 = 0, IILE_PROJ_M11 = 1, IILE_PROJ_HITHER = 2, IILE_PROJ_FOV = 3, IILE_PROJ_BOUNDS = 4 };
 
-/* PerspectiveCamera (src/cameras/perspective.cpp:50-72, src/core/camera.h:90-111). */
+/* PerspectiveCamera (src/cameras/perspective.cpp:50-72, src/core/camera.h:90-111) or EnvironmentCamera
+ * (src/cameras/environment.h:49-59), which adds no member (sizeof(iile_camera) stays 168).
+ *
+ * The environment camera has no RasterToCamera: its raster_to_camera is all zero, which no perspective camera's is (see
+ * iile_camera_kind). So that a zeroed or half-filled struct is not taken for one, it must also carry the angle
+ * that one raster step spans: dx_camera = {2 Pi / xres, 0, 0} and dy_camera = {0, Pi / yres, 0} (IILE_ENVCAM_*; xres, yres =
+ * iile_film_desc's fullResolution), with lens_radius = 0 and focal_distance = 0 (CreateEnvironmentCamera reads "lensradius" /
+ * "focaldistance" and drops them, environment.cpp:69-98). iile_scene_create refuses anything else behind a zero matrix. The
+ * two steps are a tag and a cross-check against the film, held to 1e-6 relative (however the producer rounds them): the
+ * device works the ray out from the film position and the film's resolution, operation for operation as GenerateRay does
+ * (environment.cpp:47-50), not from these two values. */
 typedef struct iile_camera {
     float raster_to_camera[16];
     float camera_to_world[16];
@@ -246,6 +256,16 @@ typedef struct iile_camera {
      * (perspective.cpp:58-62); the ray differentials of camera rays are built from them */
     float dx_camera[3], dy_camera[3];
 } iile_camera;
+enum { IILE_ENVCAM_PHI = 0 /* of dx_camera */, IILE_ENVCAM_THETA = 1 /* of dy_camera */ };
+#define IILE_CAMERA_PERSPECTIVE 0
+#define IILE_CAMERA_ENVIRONMENT 1
+/* IILE_CAMERA_* of a descriptor: the one place that reads the encoding above (the host, libiile_gpu.so's refusal pass) */
+IILE_INLINE int iile_camera_kind(const iile_camera *c) {
+    int i;
+    for (i = 0; i < 16; ++i)
+        if (c->raster_to_camera[i] != 0.f) return IILE_CAMERA_PERSPECTIVE;
+    return IILE_CAMERA_ENVIRONMENT;
+}
 
 /* Film + box filter (src/core/film.cpp:45-91, src/filters/box.cpp:41-47). */
 typedef struct iile_film_desc {

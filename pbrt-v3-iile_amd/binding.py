@@ -37,6 +37,16 @@ class HostSceneInfo(ctypes.Structure):
                                       "n_leaf_nodes n_materials n_lights xres yres spp max_depth probe_hemi_size integrator").split()]
 
 
+class Camera(ctypes.Structure):
+    """iile_camera (include/iile_scene.h). An environment camera keeps a zero raster_to_camera and the angle steps
+    2 pi / xres, pi / yres in dx_camera[0], dy_camera[1] (IILE_ENVCAM_*)."""
+    _fields_ = [("raster_to_camera", c_f32 * 16), ("camera_to_world", c_f32 * 16), ("lens_radius", c_f32), ("focal_distance", c_f32),
+                ("shutter_open", c_f32), ("shutter_close", c_f32), ("dx_camera", c_f32 * 3), ("dy_camera", c_f32 * 3)]
+
+
+CAMERA_PERSPECTIVE, CAMERA_ENVIRONMENT = range(2)  # IILE_CAMERA_* of include/iile_scene.h
+
+
 class FilmDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in "xres yres crop_x0 crop_y0 crop_x1 crop_y1 samp_x0 samp_y0 samp_x1 samp_y1".split()
                 ] + [(n, c_f32) for n in "filter_rx filter_ry scale max_sample_luminance".split()]
@@ -161,7 +171,7 @@ HOST_SYMBOLS = ["iile_host_load_pbrt", "iile_host_scene_desc", "iile_host_scene_
                 "iile_host_scene_texture", "iile_host_scene_texture_level", "iile_host_scene_filter_table",
                 "iile_host_sobol_matrices", "iile_host_sobol_vdc", "iile_host_write_exr", "iile_host_write_image",
                 "iile_host_scene_film_filename", "iile_host_scene_light", "iile_host_scene_quadric_count", "iile_host_scene_quadric",
-                "iile_host_scene_material"]
+                "iile_host_scene_material", "iile_host_scene_camera"]
 class NetWeights(ctypes.Structure):
     """iile_iispt_net_weights (include/iile_gpu.h)."""
     _fields_ = [("conv_weight", c_vp * 15), ("conv_bias", c_vp * 15), ("bn_weight", c_vp * 5), ("bn_bias", c_vp * 5),
@@ -212,6 +222,7 @@ def host_lib():
         lib.iile_host_scene_quadric_count.restype = c_i32
         lib.iile_host_scene_quadric.argtypes = [c_vp, c_i32, ctypes.POINTER(Quadric)]
         lib.iile_host_scene_material.argtypes = [c_vp, c_i32, ctypes.POINTER(Material)]
+        lib.iile_host_scene_camera.argtypes = [c_vp, ctypes.POINTER(Camera)]
         lib.iile_host_film_to_rgb.argtypes = [ctypes.POINTER(FilmDesc), c_vp, c_vp]
         lib.iile_host_write_pfm.argtypes = [ctypes.c_char_p, c_vp, c_i32, c_i32]
         lib.iile_host_read_image.argtypes = [ctypes.c_char_p, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp]
@@ -498,6 +509,14 @@ class HostScene:
         if host_lib().iile_host_scene_light(self._h, int(index), ctypes.byref(lt)) != 0:
             raise RuntimeError(host_lib().iile_host_last_error().decode())
         return lt
+
+    def camera(self):
+        """(CAMERA_PERSPECTIVE or CAMERA_ENVIRONMENT, the scene's iile_camera as a copy)."""
+        cam = Camera()
+        kind = host_lib().iile_host_scene_camera(self._h, ctypes.byref(cam))
+        if kind < 0:
+            raise RuntimeError(host_lib().iile_host_last_error().decode())
+        return int(kind), cam
 
     @property
     def quadric_count(self):

@@ -364,7 +364,7 @@ int run_pass(iile_scene *sc, const DScene &S, int max_depth, const PassDesc &P_i
     PassBuffers &B = sc->pb;
     PassDesc P = P_in;
     // camera rays made inside the first extend / shade (see PassDesc::gen_fused) where nothing else reads queue 0
-    P.gen_fused = !cfg.count_stats && !P.list_px && !S.has_infinite && !S.probe_mode && !B.nray_out;
+    P.gen_fused = !cfg.count_stats && !P.list_px && !S.has_infinite && !S.probe_mode && !B.nray_out && !S.env_camera;  // (camera_ray<false>)
     HIP_TRY(hipMemsetAsync(B.counts, 0, kCntWords * sizeof(uint32_t), cfg.stream));
     auto timed_launch_on = [&](hipStream_t stream, int kind, auto &&fn) -> int {
         EventPair *ep = nullptr;
@@ -649,6 +649,20 @@ int check_scene_desc(const iile_scene_desc &d) {
         return fail(IILE_ERR_ARG, "iile_sobol: bad dimension count / resolution, or sample indices beyond 32 bits");
     if (sb.enabled && (sb.resolution < d.film.samp_x1 - d.film.samp_x0 || sb.resolution < d.film.samp_y1 - d.film.samp_y0))
         return fail(IILE_ERR_ARG, "iile_sobol: resolution smaller than the sample bounds");
+    // an all-zero raster_to_camera stands for the environment camera (iile_camera, iile_scene.h) only together with the rest of
+    // its encoding: a zeroed struct, or a perspective camera that lost its matrix, is neither camera
+    const iile_camera &cam = d.camera;
+    if (iile_camera_kind(&cam) == IILE_CAMERA_ENVIRONMENT) {
+        const float dphi = cam.dx_camera[IILE_ENVCAM_PHI], dtheta = cam.dy_camera[IILE_ENVCAM_THETA];
+        // (the steps are a tag the device does not compute with — it follows environment.cpp from the film's resolution — so a
+        // producer that rounds them another way is not refused: a few ulps of slack, 1e-6 relative)
+        const auto near = [](float v, float want) { return std::isfinite(v) && v > 0 && std::abs(v - want) <= 1e-6f * want; };
+        const bool steps = d.film.xres > 0 && d.film.yres > 0 && near(dphi, 2 * kPi / float(d.film.xres)) &&
+                           near(dtheta, kPi / float(d.film.yres)) && cam.dx_camera[1] == 0 && cam.dx_camera[2] == 0 &&
+                           cam.dy_camera[0] == 0 && cam.dy_camera[2] == 0;
+        if (!steps || cam.lens_radius != 0)
+            return fail(IILE_ERR_ARG, "environment camera: a zero raster_to_camera needs lens_radius 0 and the angle steps 2 pi / xres, pi / yres");
+    }
     return IILE_OK;
 }
 
@@ -1045,6 +1059,7 @@ int build_camera_film(iile_scene *sc, const iile_scene_desc &d) {
     std::memcpy(S.raster_to_camera.m, d.camera.raster_to_camera, 64);
     std::memcpy(S.camera_to_world.m, d.camera.camera_to_world, 64);
     S.lens_radius = d.camera.lens_radius, S.focal_distance = d.camera.focal_distance;
+    S.env_camera = iile_camera_kind(&d.camera) == IILE_CAMERA_ENVIRONMENT ? 1 : 0;
     std::memcpy(S.dx_camera, d.camera.dx_camera, sizeof(S.dx_camera));
     std::memcpy(S.dy_camera, d.camera.dy_camera, sizeof(S.dy_camera));
     S.diff_scale = 1 / std::sqrt(float(d.halton.spp));  // integrator.cpp:284-285

@@ -239,7 +239,7 @@ DEV F3 cosine_sample_hemisphere(float u0, float u1) {
 }
 
 // ===========================================================================
-// camera (cameras/perspective.cpp:100-149, core/transform.h:251-264)
+// camera (cameras/perspective.cpp:100-149, cameras/environment.cpp:43-56, core/transform.h:251-264)
 // ===========================================================================
 // `zero` is 0.f: a caller inside a persistent loop passes one the compiler cannot see through (opaque_zero), so that the
 // products of matrix entries (SGPRs) with it are worked out where they are used instead of being hoisted out of the loop
@@ -249,20 +249,42 @@ DEV float opaque_zero() {
     asm volatile("" : "+v"(z));
     return z;
 }
+// EnvironmentCamera::GenerateRay's direction (environment.cpp:47-50), not normalised. A call, not inline code: the kind is a
+// scene constant, and inline the double-precision sine and cosine of this branch changed the register allocation (scratch,
+// VGPRs) of every kernel that makes a perspective camera ray.
+static __device__ __attribute__((noinline)) F3 env_camera_direction(float pfx, float pfy, int xres, int yres) {
+    const float theta = kPi * pfy / float(yres);
+    const float phi = 2 * kPi * pfx / float(xres);
+    float st, ct, sp, cp;
+    sincos_f(theta, &st, &ct);
+    sincos_f(phi, &sp, &cp);
+    return F3{st * cp, ct, st * sp};
+}
+// ANY_CAMERA = false: the perspective camera alone, for the two sites that make their camera ray inside a persistent traversal /
+// shading loop (PassDesc::gen_fused, which a pass with an environment camera does not set): with the other camera's branch in
+// them, k_extend<.., GEN> and the plain k_shade take more scratch, whichever way that branch is compiled.
+template <bool ANY_CAMERA = true>
 DEV void camera_ray(const DScene &S, float pfx, float pfy, float lu0, float lu1, F3 *o_out, F3 *d_out, float *tmax,
                     const float zero = 0.f) {
-    F3 pcam = xf_point(S.raster_to_camera, F3{pfx, pfy, zero});
     F3 ro = F3{zero, zero, zero};
-    F3 rd = normalize(pcam);
-    if (S.lens_radius > 0) {
-        float lx, ly;
-        concentric_sample_disk(lu0, lu1, &lx, &ly);
-        lx = S.lens_radius * lx;
-        ly = S.lens_radius * ly;
-        float ft = S.focal_distance / rd.z;
-        F3 pfocus = ro + rd * ft;
-        ro = F3{lx, ly, zero};
-        rd = normalize(pfocus - ro);
+    F3 rd;
+    if (ANY_CAMERA && S.env_camera) {
+        // the origin is (0, 0, 0), there is no lens (environment.cpp:51). (S.xres / S.yres are the frame's: the probe pass,
+        // which swaps them, makes probe_ray's rays.)
+        rd = env_camera_direction(pfx, pfy, S.xres, S.yres);
+    } else {
+        F3 pcam = xf_point(S.raster_to_camera, F3{pfx, pfy, zero});
+        rd = normalize(pcam);
+        if (S.lens_radius > 0) {
+            float lx, ly;
+            concentric_sample_disk(lu0, lu1, &lx, &ly);
+            lx = S.lens_radius * lx;
+            ly = S.lens_radius * ly;
+            float ft = S.focal_distance / rd.z;
+            F3 pfocus = ro + rd * ft;
+            ro = F3{lx, ly, zero};
+            rd = normalize(pfocus - ro);
+        }
     }
     F3 oerr;
     F3 o = xf_point_err(S.camera_to_world, ro, &oerr);
@@ -308,7 +330,28 @@ DEV void probe_ray(const DScene &S, const DProbeCam &cam, float pfx, float pfy, 
 struct RayDiff {
     F3 rxo, ryo, rxd, ryd;
 };
+// The environment camera has no GenerateRayDifferential of its own: Camera::GenerateRayDifferential (camera.cpp:60-96), the
+// rays through the film points shifted by eps = 0.05 in x and in y, differenced (every ray's weight is 1, so the -0.05 retry
+// never runs); then ScaleDifferentials
+DEV RayDiff env_camera_differentials(const DScene &S, float pfx, float pfy, F3 o, F3 d) {
+    const float eps = .05f;
+    F3 xo, xd, yo, yd;
+    float tm;
+    camera_ray(S, pfx + eps, pfy, 0.f, 0.f, &xo, &xd, &tm);
+    camera_ray(S, pfx, pfy + eps, 0.f, 0.f, &yo, &yd, &tm);
+    const float inv = 1.f / eps;  // Vector3::operator/ multiplies by the reciprocal
+    const F3 rxo = o + (xo - o) * inv, rxd = d + (xd - d) * inv;
+    const F3 ryo = o + (yo - o) * inv, ryd = d + (yd - d) * inv;
+    const float sc = S.diff_scale;
+    RayDiff r;
+    r.rxo = o + (rxo - o) * sc;
+    r.ryo = o + (ryo - o) * sc;
+    r.rxd = d + (rxd - d) * sc;
+    r.ryd = d + (ryd - d) * sc;
+    return r;
+}
 DEV RayDiff camera_differentials(const DScene &S, float pfx, float pfy, float lu0, float lu1, F3 o, F3 d) {
+    if (S.env_camera) return env_camera_differentials(S, pfx, pfy, o, d);
     const F3 pcam = xf_point(S.raster_to_camera, F3{pfx, pfy, 0});
     const F3 dxc = F3{S.dx_camera[0], S.dx_camera[1], S.dx_camera[2]}, dyc = F3{S.dy_camera[0], S.dy_camera[1], S.dy_camera[2]};
     F3 rxo = F3{0, 0, 0}, ryo = F3{0, 0, 0}, rxd, ryd;

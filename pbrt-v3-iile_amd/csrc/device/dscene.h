@@ -182,6 +182,7 @@ struct DScene {
     M44 raster_to_camera, camera_to_world;
     float lens_radius, focal_distance;
     float dx_camera[3], dy_camera[3];  // PerspectiveCamera::dxCamera / dyCamera
+    int env_camera;                    // EnvironmentCamera (iile_camera_kind): camera_ray / camera_differentials take their other branch
     float diff_scale;                  // 1 / sqrt(spp): ScaleDifferentials of the render loop
     // film
     int xres, yres;

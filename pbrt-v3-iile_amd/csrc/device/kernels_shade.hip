@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                     }
                     F3 co, cd;
                     float ctm;
-                    camera_ray(S, cpf.x, cpf.y, cl0, cl1, &co, &cd, &ctm, opaque_zero());
+                    camera_ray<false>(S, cpf.x, cpf.y, cl0, cl1, &co, &cd, &ctm, opaque_zero());  // (gen_fused: never an environment camera)
                     o4 = make_float4(co.x, co.y, co.z, b2f(slot));
                     d4 = make_float4(cd.x, cd.y, cd.z, ctm);
                 } else {

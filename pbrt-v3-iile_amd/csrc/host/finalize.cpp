@@ -218,37 +218,50 @@ bool finalize_scene(HostScene *s, std::string *err) {
     }
 
     // Camera, cameras/perspective.cpp:297-330 and core/camera.h:90-111
-    float frame = s->frame_aspect > 0 ? s->frame_aspect : float(s->xres) / float(s->yres);
-    float sw[4];  // pMin.x, pMax.x, pMin.y, pMax.y
-    if (frame > 1.f) {
-        sw[0] = -frame;
-        sw[1] = frame;
-        sw[2] = -1.f;
-        sw[3] = 1.f;
-    } else {
-        sw[0] = -1.f;
-        sw[1] = 1.f;
-        sw[2] = -1.f / frame;
-        sw[3] = 1.f / frame;
-    }
-    if (s->has_screen_window)
-        for (int i = 0; i < 4; ++i) sw[i] = s->screen_window[i];
-    Xform camera_to_screen = xf_perspective(s->fov, 1e-2f, 1000.f);
-    Xform screen_to_raster = xf_scale(float(s->xres), float(s->yres), 1) *
-                             xf_scale(1 / (sw[1] - sw[0]), 1 / (sw[2] - sw[3]), 1) *
-                             xf_translate(V3(-sw[0], -sw[3], 0));
-    Xform raster_to_screen = inverse(screen_to_raster);
-    Xform raster_to_camera = inverse(camera_to_screen) * raster_to_screen;
-    std::memcpy(d.camera.raster_to_camera, raster_to_camera.m.m, sizeof(float) * 16);
     std::memcpy(d.camera.camera_to_world, s->camera_to_world.m.m, sizeof(float) * 16);
-    {  // PerspectiveCamera ctor, perspective.cpp:58-62
-        V3 o = raster_to_camera.point(V3(0, 0, 0));
-        V3 dx = raster_to_camera.point(V3(1, 0, 0)) - o, dy = raster_to_camera.point(V3(0, 1, 0)) - o;
-        d.camera.dx_camera[0] = dx.x, d.camera.dx_camera[1] = dx.y, d.camera.dx_camera[2] = dx.z;
-        d.camera.dy_camera[0] = dy.x, d.camera.dy_camera[1] = dy.y, d.camera.dy_camera[2] = dy.z;
+    if (s->camera_name == "environment") {
+        // EnvironmentCamera (environment.h:49-59, CreateEnvironmentCamera, environment.cpp:58-101): no projection, no lens
+        // ("lensradius", "focaldistance", "frameaspectratio" and "screenwindow" are read and dropped: none of the perspective
+        // set-up below runs, so a "screenwindow" that is no window is never inverted). The encoding: include/iile_scene.h, iile_camera
+        std::memset(d.camera.raster_to_camera, 0, sizeof(d.camera.raster_to_camera));
+        std::memset(d.camera.dx_camera, 0, sizeof(d.camera.dx_camera));
+        std::memset(d.camera.dy_camera, 0, sizeof(d.camera.dy_camera));
+        d.camera.dx_camera[IILE_ENVCAM_PHI] = 2 * kPi / float(s->xres);
+        d.camera.dy_camera[IILE_ENVCAM_THETA] = kPi / float(s->yres);
+        d.camera.lens_radius = 0.f;
+        d.camera.focal_distance = 0.f;
+    } else {
+        float frame = s->frame_aspect > 0 ? s->frame_aspect : float(s->xres) / float(s->yres);
+        float sw[4];  // pMin.x, pMax.x, pMin.y, pMax.y
+        if (frame > 1.f) {
+            sw[0] = -frame;
+            sw[1] = frame;
+            sw[2] = -1.f;
+            sw[3] = 1.f;
+        } else {
+            sw[0] = -1.f;
+            sw[1] = 1.f;
+            sw[2] = -1.f / frame;
+            sw[3] = 1.f / frame;
+        }
+        if (s->has_screen_window)
+            for (int i = 0; i < 4; ++i) sw[i] = s->screen_window[i];
+        Xform camera_to_screen = xf_perspective(s->fov, 1e-2f, 1000.f);
+        Xform screen_to_raster = xf_scale(float(s->xres), float(s->yres), 1) *
+                                 xf_scale(1 / (sw[1] - sw[0]), 1 / (sw[2] - sw[3]), 1) *
+                                 xf_translate(V3(-sw[0], -sw[3], 0));
+        Xform raster_to_screen = inverse(screen_to_raster);
+        Xform raster_to_camera = inverse(camera_to_screen) * raster_to_screen;
+        std::memcpy(d.camera.raster_to_camera, raster_to_camera.m.m, sizeof(float) * 16);
+        {  // PerspectiveCamera ctor, perspective.cpp:58-62
+            V3 o = raster_to_camera.point(V3(0, 0, 0));
+            V3 dx = raster_to_camera.point(V3(1, 0, 0)) - o, dy = raster_to_camera.point(V3(0, 1, 0)) - o;
+            d.camera.dx_camera[0] = dx.x, d.camera.dx_camera[1] = dx.y, d.camera.dx_camera[2] = dx.z;
+            d.camera.dy_camera[0] = dy.x, d.camera.dy_camera[1] = dy.y, d.camera.dy_camera[2] = dy.z;
+        }
+        d.camera.lens_radius = s->lens_radius;
+        d.camera.focal_distance = s->focal_distance;
     }
-    d.camera.lens_radius = s->lens_radius;
-    d.camera.focal_distance = s->focal_distance;
     d.camera.shutter_open = s->shutter_open;
     d.camera.shutter_close = s->shutter_close;
 

@@ -86,6 +86,15 @@ int iile_host_scene_light(const iile_host_scene *scene, int32_t index, iile_ligh
     return 0;
 }
 
+int iile_host_scene_camera(const iile_host_scene *scene, iile_camera *out) {
+    if (!scene || !out) {
+        g_err = "iile_host_scene_camera: null argument";
+        return -1;
+    }
+    *out = scene->s.desc.camera;
+    return iile_camera_kind(out);
+}
+
 int iile_host_scene_get_info(const iile_host_scene *scene, iile_host_scene_info *info) {
     if (!scene || !info) {
         g_err = "iile_host_scene_get_info: null argument";

@@ -410,8 +410,10 @@ class Loader {
 
     bool directive(const std::string &d, const std::string &name, const ParamSet &ps) {
         HostScene &s = *scene_;
-        if (d == "Camera") {  // api.cpp:1118-1123, cameras/perspective.cpp:283-330
-            if (name != "perspective") return fail("only the perspective camera is supported, got " + name);
+        if (d == "Camera") {  // api.cpp:1118-1123, cameras/perspective.cpp:283-330, cameras/environment.cpp:58-101
+            // (the environment camera reads the common parameters below and drops all but the shutter: finalize.cpp)
+            if (name != "perspective" && name != "environment")
+                return fail("only the perspective and environment cameras are supported, got " + name);
             s.camera_name = name;
             s.camera_to_world = inverse(ctm_);
             named_cs_["camera"] = s.camera_to_world;
