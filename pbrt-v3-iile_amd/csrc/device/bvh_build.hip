@@ -31,17 +31,10 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/iile_gpu.h"
-#include "kernels.h"
+#include "api_common.h"
 
 namespace iile {
 namespace {
-
-#define HIP_TRYB(expr)                                                                            \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return api_fail(IILE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr int kBB = 256;
 constexpr float kFltMax = 3.402823466e+38f;
@@ -681,13 +674,13 @@ int device_scan(const int *in, int *out, size_t n64, bool inclusive, hipStream_t
         return IILE_OK;
     }
     Dev<int> sums, offs;
-    HIP_TRYB(sums.alloc(size_t(tiles)));
-    HIP_TRYB(offs.alloc(size_t(tiles)));
+    HIP_TRY(sums.alloc(size_t(tiles)));
+    HIP_TRY(offs.alloc(size_t(tiles)));
     hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(kBB), 0, s, in, out, n, sums.p, inclusive ? 1 : 0);
     const int rc = device_scan(sums.p, offs.p, size_t(tiles), false, s);
     if (rc) return rc;
     hipLaunchKernelGGL(k_scan_add, dim3(tiles), dim3(kBB), 0, s, out, n, offs.p);
-    HIP_TRYB(hipStreamSynchronize(s));  // (the two scratch arrays die with this scope)
+    HIP_TRY(hipStreamSynchronize(s));  // (the two scratch arrays die with this scope)
     return IILE_OK;
 }
 
@@ -748,10 +741,10 @@ int device_sort_pairs_30(uint32_t *keys, int *vals, uint32_t *keys_out, int *val
     Dev<int> counts, offsets;
     Dev<uint32_t> keys_tmp;
     Dev<int> vals_tmp;
-    HIP_TRYB(counts.alloc(size_t(kSortDigits) * tiles));
-    HIP_TRYB(offsets.alloc(size_t(kSortDigits) * tiles));
-    HIP_TRYB(keys_tmp.alloc(size_t(n)));
-    HIP_TRYB(vals_tmp.alloc(size_t(n)));
+    HIP_TRY(counts.alloc(size_t(kSortDigits) * tiles));
+    HIP_TRY(offsets.alloc(size_t(kSortDigits) * tiles));
+    HIP_TRY(keys_tmp.alloc(size_t(n)));
+    HIP_TRY(vals_tmp.alloc(size_t(n)));
     // five passes: in -> tmp -> out -> tmp -> out -> ... ending in `out` (the inputs stay untouched)
     const uint32_t *src_k = keys;
     const int *src_v = vals;
@@ -767,8 +760,8 @@ int device_sort_pairs_30(uint32_t *keys, int *vals, uint32_t *keys_out, int *val
         src_k = dst_k;
         src_v = dst_v;
     }
-    HIP_TRYB(hipGetLastError());
-    HIP_TRYB(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
     return IILE_OK;
 }
 
@@ -841,25 +834,25 @@ __global__ __launch_bounds__(kBB) void k_pack_wide(int n, const iile_bvh_node *n
 
 }  // namespace
 
-// Validates the child indices and leaf ranges of a flattened tree on the host side of the caller (api.hip) before this.
+// Validates the child indices and leaf ranges of a flattened tree on the host side of the caller (check_bvh_nodes, api_scene.hip) before this.
 int pack_wide_records(const iile_bvh_node *d_nodes, int n_nodes, int n_interior, float4 *d_wide, float4 *d_wide4, int *nested_out,
                       const int *d_remap) {
     *nested_out = 1;
     if (n_nodes <= 0) return IILE_OK;
     Dev<int> flags, excl, bad;
-    HIP_TRYB(flags.alloc(size_t(n_nodes)));
-    HIP_TRYB(excl.alloc(size_t(n_nodes)));
-    HIP_TRYB(bad.alloc(1));
-    HIP_TRYB(hipMemsetAsync(bad.p, 0, sizeof(int), nullptr));
+    HIP_TRY(flags.alloc(size_t(n_nodes)));
+    HIP_TRY(excl.alloc(size_t(n_nodes)));
+    HIP_TRY(bad.alloc(1));
+    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), nullptr));
     hipLaunchKernelGGL(k_interior_flags, dim3(grid_for(n_nodes)), dim3(kBB), 0, nullptr, n_nodes, d_nodes, flags.p);
     {
         const int rc = device_scan(flags.p, excl.p, size_t(n_nodes), false, nullptr);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_pack_wide, dim3(grid_for(n_nodes)), dim3(kBB), 0, nullptr, n_nodes, d_nodes, excl.p, d_remap, d_wide, d_wide4, bad.p);
-    HIP_TRYB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     int not_nested = 0;
-    HIP_TRYB(hipMemcpy(&not_nested, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&not_nested, bad.p, sizeof(int), hipMemcpyDeviceToHost));
     *nested_out = not_nested ? 0 : 1;
     (void)n_interior;
     return IILE_OK;
@@ -873,9 +866,7 @@ extern "C" int iile_bvh_build_hlbvh(int32_t n_prims, const float *bounds6, int32
                                     int32_t *n_nodes_out, int32_t *order_out, iile_bvh_build_stats *stats) {
     if (n_prims < 0 || (n_prims > 0 && (!bounds6 || !nodes_out || !order_out)) || !n_nodes_out)
         return api_fail(IILE_ERR_ARG, "iile_bvh_build_hlbvh: null argument");
-    int dev_count = 0;
-    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count <= 0)
-        return api_fail(IILE_ERR_NO_DEVICE, "no HIP device available: libiile_gpu has no CPU fallback (iile_bvh_build_hlbvh)");
+    if (const int rc = ensure_device()) return rc;
     iile_bvh_build_stats st;
     std::memset(&st, 0, sizeof(st));
     *n_nodes_out = 0;
@@ -895,65 +886,65 @@ extern "C" int iile_bvh_build_hlbvh(int32_t n_prims, const float *bounds6, int32
                 if (e[i]) (void)hipEventDestroy(e[i]);
         }
     } guard{ev};
-    for (hipEvent_t &e : ev) HIP_TRYB(hipEventCreate(&e));
+    for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
     hipStream_t s = nullptr;
 
     Dev<float> d_bounds;
     Dev<uint32_t> keys6, codes, codes_sorted;
     Dev<int> numbers, numbers_sorted, flags, incl, starts, n_nodes_t, base;
     Dev<iile_bvh_node> pool, out;
-    HIP_TRYB(d_bounds.alloc(6 * size_t(n)));
-    HIP_TRYB(keys6.alloc(6));
-    HIP_TRYB(codes.alloc(size_t(n)));
-    HIP_TRYB(codes_sorted.alloc(size_t(n)));
-    HIP_TRYB(numbers.alloc(size_t(n)));
-    HIP_TRYB(numbers_sorted.alloc(size_t(n)));
-    HIP_TRYB(flags.alloc(size_t(n)));
-    HIP_TRYB(incl.alloc(size_t(n)));
-    HIP_TRYB(starts.alloc(size_t(n) + 1));
-    HIP_TRYB(pool.alloc(2 * size_t(n)));
+    HIP_TRY(d_bounds.alloc(6 * size_t(n)));
+    HIP_TRY(keys6.alloc(6));
+    HIP_TRY(codes.alloc(size_t(n)));
+    HIP_TRY(codes_sorted.alloc(size_t(n)));
+    HIP_TRY(numbers.alloc(size_t(n)));
+    HIP_TRY(numbers_sorted.alloc(size_t(n)));
+    HIP_TRY(flags.alloc(size_t(n)));
+    HIP_TRY(incl.alloc(size_t(n)));
+    HIP_TRY(starts.alloc(size_t(n) + 1));
+    HIP_TRY(pool.alloc(2 * size_t(n)));
     // (everything is allocated before the first kernel: a hipMalloc between two stages costs more than the upper tree's kernel)
     Dev<Box> d_roots, d_cbox;
     Dev<int> up_ints;  // the upper tree's index arrays, queues and per-node words (UpperDev), one allocation
-    HIP_TRYB(d_roots.alloc(size_t(kUpMax)));
-    HIP_TRYB(d_cbox.alloc(size_t(kUpMax)));
-    HIP_TRYB(up_ints.alloc(14 * size_t(kUpMax) + 8));
-    HIP_TRYB(out.alloc(2 * size_t(n)));  // 2 n - 1 nodes at most (one primitive per leaf)
+    HIP_TRY(d_roots.alloc(size_t(kUpMax)));
+    HIP_TRY(d_cbox.alloc(size_t(kUpMax)));
+    HIP_TRY(up_ints.alloc(14 * size_t(kUpMax) + 8));
+    HIP_TRY(out.alloc(2 * size_t(n)));  // 2 n - 1 nodes at most (one primitive per leaf)
     Dev<int> arena;  // emitLBVH's eleven int arrays of n (+ 1) entries in one allocation
     const size_t stride = (size_t(n) + 1 + 63) & ~size_t(63);
-    HIP_TRYB(arena.alloc(11 * stride));
-    HIP_TRYB(n_nodes_t.alloc(size_t(kUpMax)));
-    HIP_TRYB(base.alloc(size_t(kUpMax)));
+    HIP_TRY(arena.alloc(11 * stride));
+    HIP_TRY(n_nodes_t.alloc(size_t(kUpMax)));
+    HIP_TRY(base.alloc(size_t(kUpMax)));
     Dev<int> err_flag;
-    HIP_TRYB(err_flag.alloc(1));
-    HIP_TRYB(hipMemcpyAsync(d_bounds.p, bounds6, 6 * size_t(n) * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(err_flag.alloc(1));
+    HIP_TRY(hipMemcpyAsync(d_bounds.p, bounds6, 6 * size_t(n) * sizeof(float), hipMemcpyHostToDevice, s));
     const uint32_t key_init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    HIP_TRYB(hipMemcpyAsync(keys6.p, key_init, sizeof(key_init), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(keys6.p, key_init, sizeof(key_init), hipMemcpyHostToDevice, s));
 
-    HIP_TRYB(hipEventRecord(ev[0], s));
+    HIP_TRY(hipEventRecord(ev[0], s));
     hipLaunchKernelGGL(k_centroid_bounds, dim3(std::min(grid_for(n), 512)), dim3(kBB), 0, s, n, d_bounds.p, keys6.p);
     hipLaunchKernelGGL(k_morton, dim3(grid_for(n)), dim3(kBB), 0, s, n, d_bounds.p, keys6.p, codes.p, numbers.p);
-    HIP_TRYB(hipEventRecord(ev[1], s));
+    HIP_TRY(hipEventRecord(ev[1], s));
     {
         const int rc = device_sort_pairs_30(codes.p, numbers.p, codes_sorted.p, numbers_sorted.p, n, s);
         if (rc) return rc;
     }
-    HIP_TRYB(hipEventRecord(ev[2], s));
+    HIP_TRY(hipEventRecord(ev[2], s));
     hipLaunchKernelGGL(k_treelet_flags, dim3(grid_for(n)), dim3(kBB), 0, s, n, codes_sorted.p, flags.p);
     {
         const int rc = device_scan(flags.p, incl.p, size_t(n), true, s);
         if (rc) return rc;
-        HIP_TRYB(hipStreamSynchronize(s));
+        HIP_TRY(hipStreamSynchronize(s));
     }
     hipLaunchKernelGGL(k_treelet_starts, dim3(grid_for(n)), dim3(kBB), 0, s, n, flags.p, incl.p, starts.p);
     int n_treelets = 0;  // runs of equal top 12 bits: at most 4096 (read back with the split count below)
-    HIP_TRYB(hipMemsetAsync(err_flag.p, 0, sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(err_flag.p, 0, sizeof(int), s));
     int n_splits = 0, h_err = 0;
     {
         int *ap[11];
         for (int k = 0; k < 11; ++k) ap[k] = arena.p + size_t(k) * stride;
         int *const aEnds = ap[7], *const aPE = ap[8], *const aI = ap[3], *const aF = ap[4];
-        HIP_TRYB(hipMemsetAsync(aEnds, 0, (size_t(n) + 1) * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(aEnds, 0, (size_t(n) + 1) * sizeof(int), s));
         LbvhArrays A{codes_sorted.p, numbers_sorted.p, flags.p, incl.p, starts.p, ap[0], ap[1], ap[2], aI, aF, ap[5],
                      ap[6], aEnds, aPE, ap[9], ap[10]};
         hipLaunchKernelGGL(k_lbvh_ranges, dim3(grid_for(n)), dim3(kBB), 0, s, n, A, max_prims);
@@ -965,15 +956,15 @@ extern "C" int iile_bvh_build_hlbvh(int32_t n_prims, const float *bounds6, int32
         hipLaunchKernelGGL(k_lbvh_interior, dim3(grid_for(n)), dim3(kBB), 0, s, n, A, pool.p);
         hipLaunchKernelGGL(k_lbvh_leaves, dim3(grid_for(n)), dim3(kBB), 0, s, n, A, d_bounds.p, pool.p, n_nodes_t.p, err_flag.p);
         for (int bit = 0; bit < 18; ++bit) hipLaunchKernelGGL(k_lbvh_join, dim3(grid_for(n)), dim3(kBB), 0, s, n, A, pool.p, bit);
-        HIP_TRYB(hipGetLastError());
-        HIP_TRYB(hipMemcpyAsync(&n_splits, aF + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRYB(hipMemcpyAsync(&h_err, err_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRYB(hipMemcpyAsync(&n_treelets, incl.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRYB(hipStreamSynchronize(s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&n_splits, aF + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&h_err, err_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&n_treelets, incl.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
     }
     if (h_err) return api_fail(IILE_ERR_UNSUPPORTED, "iile_bvh_build_hlbvh: a leaf holds more than 65535 primitives (equal Morton codes)");
     if (n_treelets > kUpMax) return api_fail(IILE_ERR_UNSUPPORTED, "iile_bvh_build_hlbvh: more than 4096 treelets");
-    HIP_TRYB(hipEventRecord(ev[3], s));
+    HIP_TRY(hipEventRecord(ev[3], s));
     // buildUpperSAH + the preorder offsets of all subtrees, on the device: every treelet has emitted n_nodes_t nodes, the
     // upper tree adds n_treelets - 1
     const int n_upper = n_treelets - 1;
@@ -1005,8 +996,8 @@ extern "C" int iile_bvh_build_hlbvh(int32_t n_prims, const float *bounds6, int32
         for (int l0 = 0; l0 < n_upper; l0 += batch) {
             const int l1 = std::min(l0 + batch, n_upper);
             for (int level = l0; level < l1; ++level) hipLaunchKernelGGL(k_upper_split, dim3(split_blocks), dim3(kBB), 0, s, level, U);
-            HIP_TRYB(hipMemcpyAsync(level_count.data() + l0, U.qcount + l0, size_t(l1 - l0 + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRYB(hipStreamSynchronize(s));
+            HIP_TRY(hipMemcpyAsync(level_count.data() + l0, U.qcount + l0, size_t(l1 - l0 + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
             depth = l1;
             bool done = false;
             for (int level = l0; level <= l1 && !done; ++level)
@@ -1015,14 +1006,14 @@ extern "C" int iile_bvh_build_hlbvh(int32_t n_prims, const float *bounds6, int32
         }
         hipLaunchKernelGGL(k_upper_finish, dim3(1), dim3(kUpFinishThreads), 0, s, n_treelets, depth, U);
     }
-    HIP_TRYB(hipEventRecord(ev[4], s));
+    HIP_TRY(hipEventRecord(ev[4], s));
     hipLaunchKernelGGL(k_place_nodes, dim3(grid_for(2 * n)), dim3(kBB), 0, s, n, incl.p, starts.p, n_nodes_t.p, base.p, pool.p, out.p);
-    HIP_TRYB(hipGetLastError());
-    HIP_TRYB(hipEventRecord(ev[5], s));
-    HIP_TRYB(hipMemcpyAsync(nodes_out, out.p, size_t(n_nodes) * sizeof(iile_bvh_node), hipMemcpyDeviceToHost, s));
-    HIP_TRYB(hipMemcpyAsync(order_out, numbers_sorted.p, size_t(n) * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRYB(hipEventRecord(ev[6], s));
-    HIP_TRYB(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[5], s));
+    HIP_TRY(hipMemcpyAsync(nodes_out, out.p, size_t(n_nodes) * sizeof(iile_bvh_node), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(order_out, numbers_sorted.p, size_t(n) * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(ev[6], s));
+    HIP_TRY(hipStreamSynchronize(s));
     *n_nodes_out = n_nodes;
     auto ms = [&](int a, int b) {
         float v = 0;
@@ -1051,20 +1042,18 @@ extern "C" int iile_bvh_pack_probe(int32_t n_nodes, const iile_bvh_node *nodes, 
     const int bad = check_bvh_nodes(nodes, n_nodes, std::numeric_limits<int64_t>::max(), "iile_bvh_pack_probe: ", &counted);
     if (bad) return bad;
     if (counted != n_interior) return api_fail(IILE_ERR_ARG, "iile_bvh_pack_probe: n_interior does not match the tree");
-    int dev_count = 0;
-    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count <= 0)
-        return api_fail(IILE_ERR_NO_DEVICE, "no HIP device available: libiile_gpu has no CPU fallback (iile_bvh_pack_probe)");
+    if (const int rc = ensure_device()) return rc;
     Dev<iile_bvh_node> d_nodes;
     Dev<float4> w, w4;
-    HIP_TRYB(d_nodes.alloc(size_t(n_nodes)));
-    HIP_TRYB(w.alloc(4 * size_t(std::max(n_interior, 1))));
-    HIP_TRYB(w4.alloc(8 * size_t(std::max(n_interior, 1))));
-    HIP_TRYB(hipMemcpy(d_nodes.p, nodes, size_t(n_nodes) * sizeof(iile_bvh_node), hipMemcpyHostToDevice));
+    HIP_TRY(d_nodes.alloc(size_t(n_nodes)));
+    HIP_TRY(w.alloc(4 * size_t(std::max(n_interior, 1))));
+    HIP_TRY(w4.alloc(8 * size_t(std::max(n_interior, 1))));
+    HIP_TRY(hipMemcpy(d_nodes.p, nodes, size_t(n_nodes) * sizeof(iile_bvh_node), hipMemcpyHostToDevice));
     int nest = 1;
     const int rc = pack_wide_records(d_nodes.p, n_nodes, n_interior, w.p, w4.p, &nest);
     if (rc) return rc;
-    HIP_TRYB(hipMemcpy(wide16, w.p, 4 * size_t(n_interior) * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_TRYB(hipMemcpy(wide4_32, w4.p, 8 * size_t(n_interior) * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(wide16, w.p, 4 * size_t(n_interior) * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(wide4_32, w4.p, 8 * size_t(n_interior) * sizeof(float4), hipMemcpyDeviceToHost));
     *nested = nest;
     return IILE_OK;
 }

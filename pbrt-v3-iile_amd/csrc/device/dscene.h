@@ -22,12 +22,12 @@ struct DSphere {
     float radius, zmin, zmax, theta_min, theta_max, phi_max;
     int reverse_orientation, swaps_handedness;
     // (*ObjectToWorld)(Point3f(0, 0, 0)), sphere.cpp:254 / :296, worked out once at upload with xf_point's own operations
-    // (api.hip): the light-sampling code of every hit starts from it
+    // (build_shapes, api_scene.hip): the light-sampling code of every hit starts from it
     float center[3];
     float pad_;
 };
 // Disk / Cylinder (iile_quadric, shapes/disk.h:48-70, shapes/cylinder.h:48-71)
-enum { kQuadricDisk = 0, kQuadricCylinder = 1 };  // = IILE_QUADRIC_* (checked in api.hip)
+enum { kQuadricDisk = 0, kQuadricCylinder = 1 };  // = IILE_QUADRIC_* (checked in api_scene.hip)
 struct DQuadric {
     M44 o2w, o2w_inv;
     int kind;
@@ -35,7 +35,7 @@ struct DQuadric {
     int reverse_orientation, swaps_handedness;
 };
 enum { kMatMatte = 0, kMatPlastic = 1, kMatUber = 2, kMatMirror = 3, kMatGlass = 4, kMatMetal = 5, kMatSubstrate = 6,
-       kMatTranslucent = 8 };  // = IILE_MAT_* (checked in api.hip)
+       kMatTranslucent = 8 };  // = IILE_MAT_* (checked in api_scene.hip)
 // (16-byte aligned, and the fields every hit reads first: (type, kd) and (ks, alpha) are one float4 each, see make_bsdf)
 struct alignas(16) DMaterial {
     int type;
@@ -78,7 +78,7 @@ enum { kTexImage = 0, kTexScale = 1, kTexMix = 2, kTexChecker2D = 3, kTexChecker
 enum { kMapUV = 0, kMapSpherical = 1, kMapCylindrical = 2, kMapPlanar = 3 };                                          // = IILE_MAP_*
 enum { kAAClosedForm = 0, kAANone = 1 };                                                                               // = IILE_AA_*
 enum { kLightDiffuseArea = 0, kLightPoint = 1, kLightSpot = 2, kLightDistant = 3, kLightAreaTriangle = 4,
-       kLightInfinite = 5, kLightAreaQuadric = 6, kLightProjection = 7, kLightGoniometric = 8 };  // = IILE_LIGHT_* (checked in api.hip)
+       kLightInfinite = 5, kLightAreaQuadric = 6, kLightProjection = 7, kLightGoniometric = 8 };  // = IILE_LIGHT_* (checked in api_scene.hip)
 struct DLight {
     float lemit[3];  // area: Lemit; point: I
     int two_sided;
@@ -109,7 +109,7 @@ struct DHaltonDim {
 };
 constexpr int kMaxHaltonDims = 128;
 constexpr int kMaxSpheres = 8;
-constexpr int kMaxQuadrics = 1024;  // = IILE_MAX_QUADRICS (checked in api.hip)
+constexpr int kMaxQuadrics = 1024;  // = IILE_MAX_QUADRICS (checked in api_scene.hip)
 constexpr int kMaxMaterials = 64;
 constexpr int kMaxLights = 8;
 constexpr int kLightDistStride = 2 * kMaxLights + 2;  // a light distribution: func[kMaxLights], cdf[kMaxLights + 1], funcInt

@@ -10,7 +10,7 @@
 //   k_iispt_gather   the per-pixel loop (:414-596): compute_fpixel_weights (:961-1039), sample_hemisphere (:142-178) /
 //                    estimate_direct (:16-140) over the four neighbouring hemispheres the network predicted (read where
 //                    the network left them in HBM), f_beta * L
-// The host (api.hip) repeats trace + vertex until no item is left on a specular chain (at most 24 times, as the
+// The host (launch_iispt_first_hits below, for api_iispt.hip) repeats trace + vertex until no item is left on a specular chain (at most 24 times, as the
 // reference's loop). Each kernel is one thread per item and about the size of the kernel-level probes of kernels.hip:
 // a first version that ran the whole loop, traversal included, inside one kernel (245 VGPRs, 170-200 spilled SGPRs)
 // produced kernels that read outside their buffers or returned garbage for glossy hits depending on the optimisation
@@ -18,7 +18,7 @@
 // the network it sits between; it is written for exactness (bit for bit the oracle's restatement).
 // Random numbers: every film pixel draws from its own PCG32 stream RNG(rng_seed + pixel rank) (iile_iispt_task).
 #include "dpath.h"
-#include "kernels.h"
+#include "api_common.h"
 
 namespace iile {
 
@@ -97,7 +97,7 @@ DEV void vertex_state(const DScene &S, const float4 o4, const float4 d4, const f
 }
 }  // namespace
 
-// Per-item records (IisptItems, kernels.h; float4 planes of n_items each, api.hip allocates them):
+// Per-item records (IisptItems, kernels.h; float4 planes of n_items each, api_iispt.hip carves them):
 //   ro = (ray o, tMax)   rd = (ray d, bitcast {state | bounce << 8 | sampler dimension << 16})   beta = (rgb, -)
 //   hit = (bitcast prim, b0, b1, b2)   pf = (pFilm.xy, lens u)   idx[] = Halton index of the item's camera sample
 // Every kernel runs all tasks of a batch at once: blockIdx.y is the task (its IisptJob is read from HBM, uniform loads),
@@ -440,19 +440,28 @@ dim3 job_grid(int max_items, int n_jobs, const LaunchCfg &cfg) {
     return dim3(unsigned(std::max(1, std::min((max_items + kIisptBlock - 1) / kIisptBlock, budget))), unsigned(n_jobs));
 }
 }  // namespace
-void launch_iispt_first_hits(const DScene &S, const IisptJob *jobs, int n_jobs, int max_items, uint32_t *n_active, int *spill, const LaunchCfg &cfg) {
+namespace {
+int first_hits_rounds(const DScene &S, const IisptJob *jobs, int n_jobs, int max_items, uint32_t *n_active, int *spill, const LaunchCfg &cfg) {
     const dim3 grid = job_grid(max_items, n_jobs, cfg);
     hipLaunchKernelGGL(k_iispt_begin, grid, dim3(kIisptBlock), 0, cfg.stream, S, jobs);
     // find_intersection's loop: trace, then one vertex step; again while some item (of any task) follows a specular bounce
     for (int bounce = 0; bounce < 24; ++bounce) {
-        (void)hipMemsetAsync(n_active, 0, sizeof(uint32_t), cfg.stream);
+        HIP_TRY(hipMemsetAsync(n_active, 0, sizeof(uint32_t), cfg.stream));
         hipLaunchKernelGGL(k_iispt_trace, grid, dim3(kIisptBlock), 0, cfg.stream, S, jobs, spill);
         hipLaunchKernelGGL(k_iispt_vertex, grid, dim3(kIisptBlock), 0, cfg.stream, S, jobs);
         uint32_t host_active = 0;
-        if (hipMemcpyAsync(&host_active, n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, cfg.stream) != hipSuccess) return;
-        if (hipStreamSynchronize(cfg.stream) != hipSuccess) return;
+        HIP_TRY(hipMemcpyAsync(&host_active, n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, cfg.stream));
+        HIP_TRY(hipStreamSynchronize(cfg.stream));
         if (host_active == 0) break;
     }
+    return IILE_OK;
+}
+}  // namespace
+int launch_iispt_first_hits(const DScene &S, const IisptJob *jobs, int n_jobs, int max_items, uint32_t *n_active, int *spill, const LaunchCfg &cfg) {
+    const int rc = first_hits_rounds(S, jobs, n_jobs, max_items, n_active, spill, cfg);
+    // a failed round may leave copies queued, into its own counter and from the caller's host vectors: nothing may outlive them
+    if (rc) (void)hipStreamSynchronize(cfg.stream);
+    return rc;
 }
 void launch_iispt_hemi_out(const DScene &S, const IisptJob *jobs, int n_jobs, int max_hemi, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_iispt_hemi_out, job_grid(max_hemi, n_jobs, cfg), dim3(kIisptBlock), 0, cfg.stream, S, jobs);

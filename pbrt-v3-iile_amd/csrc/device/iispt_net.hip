@@ -42,11 +42,7 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/iile_gpu.h"
-
-namespace iile {
-int api_fail(int code, const std::string &msg);
-}
+#include "api_common.h"
 
 namespace {
 
@@ -864,19 +860,13 @@ struct iile_iispt_net {
     std::vector<void *> allocs;
 };
 
-#define NET_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return iile::api_fail(IILE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 namespace {
 
 int net_upload(iile_iispt_net *net, const void *host, size_t bytes, void **dev) {
     void *p = nullptr;
-    NET_TRY(hipMalloc(&p, bytes));
+    HIP_TRY(hipMalloc(&p, bytes));
     net->allocs.push_back(p);
-    NET_TRY(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
     *dev = p;
     return IILE_OK;
 }
@@ -964,9 +954,7 @@ extern "C" {
 
 int iile_iispt_net_create(const iile_iispt_net_weights *w, iile_iispt_net **out) {
     if (!w || !out) return iile::api_fail(IILE_ERR_ARG, "iile_iispt_net_create: null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return iile::api_fail(IILE_ERR_NO_DEVICE, "iile_iispt_net_create: no HIP device (the network has no CPU fallback)");
+    if (const int rc = iile::ensure_device()) return rc;
     for (int i = 0; i < 15; ++i)
         if (!w->conv_weight[i] || !w->conv_bias[i]) return iile::api_fail(IILE_ERR_ARG, "iile_iispt_net_create: missing convolution tensor");
     auto *net = new iile_iispt_net();
@@ -1079,12 +1067,12 @@ int run_layers(iile_iispt_net *net, int nb, int na, hipStream_t s, float *layer_
         a.n_img = nb;
         const bool pooled_here = kPoolInEpilogue && kRoute[l][3] == 1;
         a.pool_out = pooled_here ? buffer_of(net, BUF_R, na) : nullptr;
-        NET_TRY(launch_layer(l, a, net->n_cus, &net->attr_set[l], s));
-        if (kRoute[l][3] && !pooled_here) NET_TRY(launch_resample(l, a.out, buffer_of(net, BUF_R, na), nb, s));
+        HIP_TRY(launch_layer(l, a, net->n_cus, &net->attr_set[l], s));
+        if (kRoute[l][3] && !pooled_here) HIP_TRY(launch_resample(l, a.out, buffer_of(net, BUF_R, na), nb, s));
         if (layer_out_dev && l == layer) {   // test probe: this layer's NHWC activations, as the module has them
             size_t fl = size_t(kLayers[l].h) * kLayers[l].h * kLayers[l].cout;
             hipLaunchKernelGGL(k_net_unscale, dim3(unsigned((fl * size_t(nb) / 4 + 255) / 256)), dim3(256), 0, s, a.out, layer_out_dev + first * fl, fl * size_t(nb) / 4);
-            NET_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
     }
     return IILE_OK;
@@ -1109,12 +1097,12 @@ int iile_iispt_net_forward(iile_iispt_net *net, const float *in_dev, float *out_
         const int nb = n - first < cap ? n - first : cap;
         hipLaunchKernelGGL(k_net_input, dim3((size_t(nb) * 1024 + 255) / 256), dim3(256), 0, s, in_dev + size_t(first) * 7 * 1024,
                            buffer_of(net, BUF_P, na), nb);
-        NET_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         rc = run_layers(net, nb, na, s, layer_out_dev, layer, size_t(first));
         if (rc) return rc;
         hipLaunchKernelGGL(k_net_output, dim3((size_t(nb) * 1024 * 16 + 255) / 256), dim3(256), 0, s, buffer_of(net, BUF_Q, na), net->w_out,
                            net->b_out, out_dev + size_t(first) * 3 * 1024, nb);
-        NET_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return IILE_OK;
 }
@@ -1136,13 +1124,13 @@ int iile_iispt_net_predict(iile_iispt_net *net, const float *intensity_dev, cons
         const int nb = n - first < cap ? n - first : cap;
         hipLaunchKernelGGL(k_net_normalize, dim3(nb), dim3(256), 0, s, intensity_dev + size_t(first) * 3072, normals_dev + size_t(first) * 3072,
                            distance_dev + size_t(first) * 1024, buffer_of(net, BUF_P, na), means, nb);
-        NET_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         rc = run_layers(net, nb, na, s, nullptr, 0, 0);
         if (rc) return rc;
         hipLaunchKernelGGL(k_net_predict_out, dim3(nb), dim3(256), 0, s, buffer_of(net, BUF_Q, na), net->w_out, net->b_out, means,
                            slot_of_probe_dev ? pred_dev : pred_dev + size_t(first) * 3072, slot_of_probe_dev ? slot_of_probe_dev + first : nullptr,
                            film_rows, nb);
-        NET_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return IILE_OK;
 }

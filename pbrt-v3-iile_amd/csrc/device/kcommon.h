@@ -255,7 +255,7 @@ DEV size_t probe_record(const DScene &S, const PassDesc &P, uint32_t probe, int 
 // A film position that is a whole number (u == 0, or float(px) + u rounded to px or px + 1 where the pixel
 // coordinate is large) puts the sample into two pixels along that axis under the one-pixel box filter
 // (FilmTile::AddSample, film.h:159-166: pixels ceil(pFilm - 1) .. floor(pFilm)). Rare (1080p x 64 spp: ~1e-4 of the
-// samples); they are listed here and the pixels they touch are finished exactly by iile_render (api.hip).
+// samples); they are listed here and the pixels they touch are finished exactly by iile_render (api_render.hip).
 DEV void flag_whole_film_position(const PassBuffers &B, uint32_t pid, int px, int py, uint32_t k, float pfx, float pfy, float u0,
                                   float u1) {
     if (!B.flag_count) return;

@@ -1,4 +1,4 @@
-// kernels.h — launch interface between api.hip and kernels.hip.
+// kernels.h — launch interface between the C ABI (api_*.hip) and the kernel files.
 #pragma once
 #include <string>
 
@@ -124,9 +124,9 @@ struct LaunchCfg {
     int trav_blocks_per_cu = 0;   // persistent traversal blocks per CU; 0 = default_trav_blocks_per_cu()
 };
 
-// api.hip: records the message iile_last_error() returns, hands back `code`
+// api_scene.hip: records the message iile_last_error() returns, hands back `code`
 int api_fail(int code, const std::string &msg);
-// api.hip: the node check of a flattened tree a caller hands over (iile_scene_create, iile_bvh_pack_probe): leaf ranges in
+// api_scene.hip: the node check of a flattened tree a caller hands over (iile_scene_create, iile_bvh_pack_probe): leaf ranges in
 // [0, max_prims), an interior node's second child after it and inside the array; *n_interior = the interior nodes
 int check_bvh_nodes(const iile_bvh_node *nodes, int n_nodes, int64_t max_prims, const char *prefix, int *n_interior);
 // bvh_build.hip: two-wide (4 float4) and four-wide (8 float4) records per interior node of a flattened tree in HBM
@@ -190,7 +190,8 @@ struct IisptJob {
     float4 *out;
 };
 // camera samples + find_intersection for every item (hemi points, then film pixels) of every job; synchronises cfg.stream
-void launch_iispt_first_hits(const DScene &S, const IisptJob *jobs, int n_jobs, int max_items, uint32_t *n_active, int *spill, const LaunchCfg &cfg);
+// between its rounds, and once more before it returns the IILE_ERR_HIP of a call that failed
+int launch_iispt_first_hits(const DScene &S, const IisptJob *jobs, int n_jobs, int max_items, uint32_t *n_active, int *spill, const LaunchCfg &cfg);
 void launch_iispt_hemi_out(const DScene &S, const IisptJob *jobs, int n_jobs, int max_hemi, const LaunchCfg &cfg);
 void launch_iispt_gather(const DScene &S, const IisptJob *jobs, int n_jobs, int max_pixels, const float *jac, const LaunchCfg &cfg);
 void launch_iispt_film_add(const int4 *rects, const uint32_t *first, int n_tasks, int max_pixels, const float4 *out, double *film, int film_w, hipStream_t stream);
