@@ -176,6 +176,43 @@ int iile_bsdf_sample_ng(iile_scene *scene, int32_t n, int32_t mat, const float *
  * the null stream); the call returns when they have finished. */
 int iile_render_probes(iile_scene *scene, int32_t n_probes, const float *pos3, const float *dir3, float *intensity_rgb,
                        float *normals_xyz, float *distance, int32_t outputs_on_device, iile_stats *stats, void *stream);
+/* The probe pass of the reference mode (`pbrt --reference=N`, IISPTIntegrator::Li_reference, src/integrators/iispt.cpp:650-744): the same
+ * hemispheric cameras through IISPTdIntegrator::RenderView with a sampler of many samples per pixel — the ground-truth hemisphere `p` of a
+ * training example, next to the 1-sample d / n / z rasters that are the network's inputs. Per probe, hemi x hemi pixels in raster order:
+ *   intensity_rgb  what the probe's film holds after the samples [first_sample, first_sample + n_samples) of every pixel: for each film
+ *                  pixel the filter-weighted sum of the samples whose Gaussian footprint covers it over the sum of the weights
+ *                  (FilmTile::AddSample, Film::MergeFilmTile, Film::to_rgb_array);
+ *   weight_sum     (may be NULL) that pixel's sum of filter weights: two sample ranges of one probe merge as
+ *                  sum(intensity_i * weight_i) / sum(weight_i) — resuming, or one range per GPU;
+ *   normals_xyz / distance  (both or neither NULL) as iile_render_probes returns them, from sample first_sample alone.
+ * The reference draws a RandomSampler's samples; here sample k of a probe pixel is sample k of the probe's own Halton sampler
+ * (iile_probe_setup: HaltonSampler(1, sampleBounds)::GetIndexForSample(k)), so n_samples = 1, first_sample = 0 and the scene's probe depth
+ * give iile_render_probes' three images bit for bit. Several samples of a batch of probes run in one set of launches (path id = (probe,
+ * pixel, sample)), sized from the workspace budget and not from n_samples; every per-tile sum of a pixel grows one sample at a time in the
+ * order (sample, then sample pixel row by row), so the images do not depend on that grouping and two calls give the same bits.
+ * Refused before any launch (IILE_ERR_ARG unless noted): null pointers, n_samples < 1, first_sample < 0, max_depth outside 1 .. 14, a
+ * Halton table with fewer than 5 + 8 (max_depth + 1) + 2 dimensions (the host sizes it from the scene's maxdepth, at least 64), a sample
+ * whose Halton index leaves 32 bits (IILE_ERR_UNSUPPORTED), a probe film of more than 1024 pixels (IILE_ERR_UNSUPPORTED).
+ * stats (may be NULL): ms_total, n_passes (sets of launches), n_paths, ext_rays_traced + mis_rays_traced (closest-hit rays), workspace_bytes. */
+typedef struct iile_probe_ref_params {
+    int32_t max_depth;         /* 1 .. 14. IISPTdIntegrator's own is 3: CreateIISPTdIntegrator(dcamera, 13) hands 13 to the sampler as its
+                                  seed and hard-codes maxDepth = 3 (src/integrators/iispt_d.cpp:501-529) */
+    int32_t first_sample;      /* k of the first sample per pixel */
+    int32_t n_samples;         /* >= 1 */
+    int32_t spp_total;         /* samples per pixel of the whole image this range belongs to: ray differentials are scaled by
+                                  1 / sqrt(spp_total) as RenderView does for its sampler (iispt_d.cpp:413-414); <= 0: n_samples */
+    int32_t outputs_on_device; /* != 0: the output pointers are device memory */
+    void *stream;
+} iile_probe_ref_params;
+int iile_render_probes_reference(iile_scene *scene, int32_t n_probes, const float *pos3, const float *dir3, const iile_probe_ref_params *params,
+                                 float *intensity_rgb, float *weight_sum, float *normals_xyz, float *distance, iile_stats *stats);
+/* Test probe: force the samples per set of launches of the scene's next iile_render_probes_reference calls; 0 = sized from the budget again. */
+int iile_test_probe_ref_group(iile_scene *scene, uint32_t samples_per_group);
+/* The reference mode's points (IISPTIntegrator::render_reference / Li_reference, iispt.cpp:509-520, 650-672): for n film positions pfilm2
+ * the camera ray of CameraSample{pFilm, lens (0, 0), time 0}, its closest hit — on whatever surface: no specular chain is followed, unlike
+ * iile_iispt_hemi_points — and the aux ray isect.SpawnRay(n), n the geometric normal turned against the ray. valid[i] = 0 where the ray
+ * left the scene (pos / dir zero). Host pointers, null stream, synchronous. */
+int iile_reference_points(iile_scene *scene, int32_t n, const float *pfilm2, uint8_t *valid, float *pos3, float *dir3);
 /* The IISPT integrator's DIRECT pass: what IisptRenderRunner::run_direct
  * (src/integrators/iisptrenderrunner.cpp:601-633) leaves in film_monitor_direct — n_passes calls of
  * DirectProgressiveIntegrator::RenderOnePass (src/integrators/directprogressiveintegrator.cpp:60-150: one camera sample per

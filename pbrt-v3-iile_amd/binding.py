@@ -178,6 +178,11 @@ class NetWeights(ctypes.Structure):
                 ("bn_mean", c_vp * 5), ("bn_var", c_vp * 5), ("bn_eps", c_f32)]
 
 
+class ProbeRefParams(ctypes.Structure):  # iile_probe_ref_params
+    _fields_ = [("max_depth", c_i32), ("first_sample", c_i32), ("n_samples", c_i32), ("spp_total", c_i32), ("outputs_on_device", c_i32),
+                ("stream", c_vp)]
+
+
 class DirectParams(ctypes.Structure):  # iile_direct_params
     _fields_ = [("n_passes", ctypes.c_int32), ("first_pass", ctypes.c_int32), ("accumulate", ctypes.c_int32), ("film_on_device", ctypes.c_int32),
                 ("stream", ctypes.c_void_p)]
@@ -186,6 +191,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
                "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_render_probes",
+               "iile_render_probes_reference", "iile_test_probe_ref_group", "iile_reference_points",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
                "iile_iispt_film_add", "iile_iispt_film_merge",
@@ -305,6 +311,10 @@ def gpu_lib():
         lib.iile_light_sample_li.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp]
         lib.iile_texture_eval_p.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_render_probes.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, ctypes.POINTER(GpuStats), c_vp]
+        lib.iile_render_probes_reference.argtypes = [c_vp, c_i32, c_vp, c_vp, ctypes.POINTER(ProbeRefParams), c_vp, c_vp, c_vp, c_vp,
+                                                     ctypes.POINTER(GpuStats)]
+        lib.iile_test_probe_ref_group.argtypes = [c_vp, c_u32]
+        lib.iile_reference_points.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_bsdf_sample.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_bsdf_eval_ng.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_bsdf_sample_ng.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
@@ -733,6 +743,42 @@ class GpuScene:
         self._check(gpu_lib().iile_render_probes(self._s, n, pos.ctypes.data, direction.ctypes.data, inten.ctypes.data,
                                                  nrm.ctypes.data, dist.ctypes.data, 0, ctypes.byref(st), stream), "iile_render_probes")
         return inten, nrm, dist, st.as_dict()
+
+    def render_probes_reference(self, pos, direction, spp, max_depth=3, first_sample=0, spp_total=0, stream=None):
+        """The reference mode's probe pass (iile_render_probes_reference): samples [first_sample, first_sample + spp) of every probe pixel
+        behind the probe's filter. Returns (intensity (n, hemi, hemi, 3), weight_sum (n, hemi, hemi), normals (n, hemi, hemi, 3), distance
+        (n, hemi, hemi), stats); normals / distance are those of sample first_sample. Two ranges of one probe merge as
+        sum(intensity_i * weight_i) / sum(weight_i). max_depth: 3 is IISPTdIntegrator's own, what the reference mode renders with.
+        spp_total: the samples per pixel of the whole image the range belongs to (ray differentials); 0: spp."""
+        pos, direction = _f32(pos).reshape(-1, 3), _f32(direction).reshape(-1, 3)
+        n = len(pos)
+        hemi = int(self.host.info["probe_hemi_size"])
+        prm = ProbeRefParams(int(max_depth), int(first_sample), int(spp), int(spp_total), 0, c_vp(stream) if stream else None)
+        inten = np.zeros((n, hemi, hemi, 3), np.float32)
+        wsum = np.zeros((n, hemi, hemi), np.float32)
+        nrm = np.zeros((n, hemi, hemi, 3), np.float32)
+        dist = np.zeros((n, hemi, hemi), np.float32)
+        st = GpuStats()
+        self._check(gpu_lib().iile_render_probes_reference(self._s, n, pos.ctypes.data, direction.ctypes.data, ctypes.byref(prm), inten.ctypes.data,
+                                                           wsum.ctypes.data, nrm.ctypes.data, dist.ctypes.data, ctypes.byref(st)),
+                    "iile_render_probes_reference")
+        return inten, wsum, nrm, dist, st.as_dict()
+
+    def test_probe_ref_group(self, samples_per_group):
+        """Force the samples per set of launches of render_probes_reference (0: sized from the workspace budget again)."""
+        self._check(gpu_lib().iile_test_probe_ref_group(self._s, int(samples_per_group)), "iile_test_probe_ref_group")
+
+    def reference_points(self, pfilm):
+        """The reference mode's points (iile_reference_points) for (n, 2) film positions: (valid (n,) uint8, aux ray origins (n, 3),
+        directions (n, 3)) on the camera rays' closest hits; no specular chain is followed."""
+        pfilm = _f32(pfilm).reshape(-1, 2)
+        n = len(pfilm)
+        valid = np.zeros(n, np.uint8)
+        pos = np.zeros((n, 3), np.float32)
+        dr = np.zeros((n, 3), np.float32)
+        self._check(gpu_lib().iile_reference_points(self._s, n, pfilm.ctypes.data, valid.ctypes.data, pos.ctypes.data, dr.ctypes.data),
+                    "iile_reference_points")
+        return valid, pos, dr
 
     def iispt_hemi_points(self, task):
         """The hemi points of an IISPT task: (valid (ny, nx) uint8, aux ray origins (ny, nx, 3), directions (ny, nx, 3))."""

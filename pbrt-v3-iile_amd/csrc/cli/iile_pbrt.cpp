@@ -3,6 +3,7 @@
 //   iile_pbrt scene.pbrt [--outfile out.exr|out.pfm] [--xres N --yres N --spp N --maxdepth N] [--stats] [--gpus N]
 //             [--gpurank R/N --rendezvous FILE [--job TOKEN]]
 //             [--integrator path|iispt] [--iisptNet=FILE] [--iileIndirect=TASKS] [--iileDirect=SAMPLES] [--iispt_hemi_size=32]
+//             [--reference=N [--reference_samples=S] [--reference_resume=0|1] [--reference-list]]
 //
 // Which integrator renders the frame is the scene file's Integrator line, as in MakeIntegrator (src/core/api.cpp:1720-1750): "path" ->
 // GpuPathIntegrator, "iispt" -> GpuIisptIntegrator (csrc/host/gpu_iispt_integrator.h; --iileIndirect= / --iileDirect= /
@@ -25,6 +26,13 @@
 // R modulo N and its block of the direct passes, the two film monitors are summed on rank 0 (iile_dist_monitor_reduce), which merges and
 // writes the images.
 //
+// --reference=N is the IISPT integrator's reference mode (csrc/host/gpu_iispt_reference.h; the reference's spellings and defaults,
+// src/main/pbrt.cpp:154-166): no frame is rendered; for an N x N grid of film pixels the hemisphere at the camera ray's closest hit is
+// written to out/ as d / z / n (one sample per probe pixel: the network's inputs) and p (--reference_samples=S samples, default 4096: the
+// ground truth), plus out/train.json. $IISPT_REFERENCE_CONTROL_MOD / _MATCH pick this process's pixels as in the reference;
+// --reference_resume=1 (default) skips what is on disk already; --reference-list prints the grid and what is pending without touching a
+// device. --gpurank R/N (no rendezvous: nothing is merged) or --gpus N deal this process's pixels over GPUs.
+//
 // Mirrors src/main/pbrt.cpp:97-219 (argument loop, ParseFile, Render) on top of
 // the C ABI: libiile_host loads and flattens the scene, libiile_gpu renders it,
 // the film is normalised and written as PFM.
@@ -35,6 +43,7 @@
 #include <memory>
 
 #include "../host/gpu_iispt_integrator.h"
+#include "../host/gpu_iispt_reference.h"
 
 int main(int argc, char **argv) {
     // $IILE_TIMING: wall time of the process's phases to stderr (where does a slow start come from?)
@@ -54,10 +63,17 @@ int main(int argc, char **argv) {
     std::string rendezvous;
     iile::IisptOptions iispt;
     int integrator_choice = -1;   // --integrator: IILE_INTEGRATOR_*; -1: the scene file's
+    iile::ReferenceOptions reference;
+    bool reference_list = false;
+    const char *frame_flag = nullptr;   // the first flag that belongs to the IISPT frame (refused with --reference)
     if (const char *e = getenv("IILE_IISPT_NET")) iispt.net_file = e;
     for (int i = 1; i < argc; ++i) {
         auto arg_int = [&](int &dst) {
             if (i + 1 < argc) dst = atoi(argv[++i]);
+        };
+        auto frame_arg = [&](int skip) {   // the value of a flag of the IISPT frame
+            frame_flag = argv[i];
+            return argv[i] + skip;
         };
         // pbrt's own options keep their spellings (src/main/pbrt.cpp:106-186): --outfile, --quick, --quiet, --nthreads and
         // the logging flags are accepted (the last three change nothing here: no thread pool, no glog)
@@ -76,18 +92,26 @@ int main(int argc, char **argv) {
                   !strcmp(argv[i], "--minloglevel") || !strcmp(argv[i], "-minloglevel") || !strcmp(argv[i], "--v") || !strcmp(argv[i], "-v")) &&
                  i + 1 < argc)
             ++i;
+        else if (!strncmp(argv[i], "--reference=", 12))
+            reference.tiles = atoi(argv[i] + 12);
+        else if (!strncmp(argv[i], "--reference_samples=", 20))
+            reference.samples = atoi(argv[i] + 20);
+        else if (!strncmp(argv[i], "--reference_resume=", 19))
+            reference.resume = atoi(argv[i] + 19);
+        else if (!strcmp(argv[i], "--reference-list"))
+            reference_list = true;
         else if (!strncmp(argv[i], "--iileIndirect=", 15))
-            iispt.indirect_tasks = atoi(argv[i] + 15);
+            iispt.indirect_tasks = atoi(frame_arg(15));
         else if (!strncmp(argv[i], "--iileDirect=", 13))
-            iispt.direct_samples = atoi(argv[i] + 13);
+            iispt.direct_samples = atoi(frame_arg(13));
         else if (!strncmp(argv[i], "--iispt_hemi_size=", 18))
             iispt.hemi_size = atoi(argv[i] + 18);
         else if (!strncmp(argv[i], "--iisptNet=", 11))
-            iispt.net_file = argv[i] + 11;
+            iispt.net_file = frame_arg(11);
         else if (!strncmp(argv[i], "--iisptIndirectOut=", 19))
-            iispt.indirect_out = argv[i] + 19;
+            iispt.indirect_out = frame_arg(19);
         else if (!strncmp(argv[i], "--iisptDirectOut=", 17))
-            iispt.direct_out = argv[i] + 17;
+            iispt.direct_out = frame_arg(17);
         else if (!strcmp(argv[i], "--integrator") && i + 1 < argc) {
             const char *in = argv[++i];
             if (strcmp(in, "path") && strcmp(in, "iispt")) {
@@ -146,7 +170,8 @@ int main(int argc, char **argv) {
             fprintf(stderr, "usage: iile_pbrt scene.pbrt [--outfile f.exr|f.pfm] [--quick] [--quiet] [--nthreads N] [--xres N] [--yres N] [--spp N] "
                             "[--maxdepth N] [--stats] [--gpus N] [--sampler halton|sobol] [--splitmethod sah|hlbvh|middle|equal] [--bvh-device] "
                             "[--gpurank R/N --rendezvous FILE [--job TOKEN]] [--integrator path|iispt] [--iisptNet=FILE] [--iileIndirect=TASKS] "
-                            "[--iileDirect=SAMPLES] [--iispt_hemi_size=32] [--iisptIndirectOut=FILE] [--iisptDirectOut=FILE]\n");
+                            "[--iileDirect=SAMPLES] [--iispt_hemi_size=32] [--iisptIndirectOut=FILE] [--iisptDirectOut=FILE] "
+                            "[--reference=N [--reference_samples=S] [--reference_resume=0|1] [--reference-list]]\n");
             return 1;
         } else
             scene_file = argv[i];
@@ -161,8 +186,21 @@ int main(int argc, char **argv) {
         fprintf(stderr, "iile_pbrt: no scene file given\n");
         return 1;
     }
+    const bool reference_mode = reference.tiles > 0;
+    if (reference_list && !reference_mode) {
+        fprintf(stderr, "iile_pbrt: --reference-list lists the grid of --reference=N\n");
+        return 1;
+    }
+    if (reference_mode && frame_flag) {
+        fprintf(stderr, "iile_pbrt: --reference=N renders training hemispheres, no frame and no network: it does not go with %s\n", frame_flag);
+        return 1;
+    }
+    if (reference_mode && (reference.samples < 1 || iispt.hemi_size < 1)) {
+        fprintf(stderr, "iile_pbrt: --reference_samples wants a number >= 1\n");
+        return 1;
+    }
     iile_dist *comm = nullptr;
-    if (ranked) {
+    if (ranked && !reference_mode) {
         if (rendezvous.empty()) {
             fprintf(stderr, "iile_pbrt: --gpurank R/N needs --rendezvous FILE\n");
             return 1;
@@ -188,6 +226,44 @@ int main(int argc, char **argv) {
     lap("arguments read");
     iile::Scene scene(scene_file, ps);
     lap("scene file parsed, BVH built (host)");
+    if (reference_mode) {
+        if (!scene.ok()) return 1;
+        if (ranked && gpus_given) {
+            fprintf(stderr, "iile_pbrt: --gpurank (one process per GPU) and --gpus (one process, several devices) exclude each other\n");
+            return 1;
+        }
+        reference.rank = gpu_rank, reference.nranks = gpu_nranks;
+        reference.devices = gpus_given ? gpus : 1;
+        std::vector<iile::ReferencePixel> grid;
+        std::string why;
+        if (!iile::ReferenceGrid(scene.film(), reference, &grid, &why)) {
+            fprintf(stderr, "%s\n", why.c_str());
+            return 1;
+        }
+        if (reference_list) {
+            iile::PrintReferenceGrid(grid, reference);
+            return 0;
+        }
+        // (everything that can fail without a device has by now; the info file is the reference's first write — kept when resuming)
+        if (!iile::PrepareReferenceDirectory(reference.directory)) return 1;
+        const std::string info = reference.directory + "train.json";   // IISPT_REFERENCE_TRAIN_INFO
+        if ((reference.resume == 0 || !iile::reference_file_exists(info)) && !iile::WriteReferenceInfo(info)) return 1;
+        if (ranked) {
+            const int n_dev = iile_device_count();
+            if (n_dev < 1 || iile_device_select(gpu_rank % n_dev) != IILE_OK) {
+                fprintf(stderr, "Error: reference mode: %s\n", n_dev < 1 ? "no HIP device" : iile_last_error());
+                return 1;
+            }
+        }
+        iile::GpuIisptReference ref(reference);
+        if (!ref.Render(scene, grid)) return 1;
+        lap("reference hemispheres rendered and written");
+        if (!quiet)
+            printf("reference mode: %zu grid pixels, %lld looked at (%lld without a hit), %lld d/z/n sets, %lld p hemispheres of %d samples in %.1f ms -> %s\n",
+                   grid.size(), ref.stats.pixels, ref.stats.no_hit, ref.stats.one_sample_sets, ref.stats.reference_hemispheres, reference.samples, ref.stats.ms,
+                   reference.directory.c_str());
+        return 0;
+    }
     if (out.empty()) out = scene.ok() ? scene.film_filename() : std::string("pbrt.exr");
     if (integrator_choice < 0) integrator_choice = scene.ok() ? scene.integrator() : IILE_INTEGRATOR_PATH;
     if (integrator_choice == IILE_INTEGRATOR_IISPT) {

@@ -145,6 +145,7 @@ struct iile_scene {
     iile::DevBlock patch_block;
     iile::DevBlock film_add_block;       // iile_iispt_film_add's task table (rectangles, first pixels)
     uint32_t patch_cap_override = 0;     // iile_test_patch_capacity: hits / entries capacity forced by a test
+    uint32_t probe_ref_group_override = 0;   // iile_test_probe_ref_group: samples per set of launches of iile_render_probes_reference forced by a test
     bool overflow_unchecked = false;     // an asynchronous render left patch.counters[2] unread
     hipStream_t overflow_stream = nullptr;
     iile::DevBlock scratch;              // device scratch of the IISPT slices (scratch_reserve)

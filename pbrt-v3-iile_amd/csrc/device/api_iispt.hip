@@ -227,6 +227,31 @@ bool make_probe_camera(const float *pos, const float *dir, DProbeCam *cam) {
         for (int cidx = 0; cidx < 3; ++cidx) cam->nrm[3 * r + cidx] = minv[4 * cidx + r];  // transpose of mInv
     return true;
 }
+// the probe's film and sampler in place of the frame's, `max_depth` in place of the integrator's; diff_scale: ScaleDifferentials(1 / sqrt(samples per pixel))
+DScene probe_scene(const iile_scene *sc, int max_depth, float diff_scale) {
+    const iile_probe_setup &pr = sc->probe;
+    DScene S = sc->ds;
+    const iile_film_desc &f = pr.film;
+    S.probe_mode = 1;
+    S.xres = f.xres, S.yres = f.yres;
+    S.crop_x0 = f.crop_x0, S.crop_y0 = f.crop_y0, S.crop_x1 = f.crop_x1, S.crop_y1 = f.crop_y1;
+    S.samp_x0 = f.samp_x0, S.samp_y0 = f.samp_y0, S.samp_x1 = f.samp_x1, S.samp_y1 = f.samp_y1;
+    S.filter_rx = f.filter_rx, S.filter_ry = f.filter_ry;
+    S.max_sample_luminance = f.max_sample_luminance;
+    S.filter_wide = 1;
+    S.filter_table = sc->probe_filter_table;
+    S.pixel_offsets = sc->probe_pixel_offsets;
+    S.base_scale0 = pr.base_scales[0], S.base_scale1 = pr.base_scales[1];
+    S.base_exp0 = pr.base_exponents[0], S.base_exp1 = pr.base_exponents[1];
+    S.sample_stride = pr.sample_stride;
+    S.mult_inv0 = pr.mult_inverse[0], S.mult_inv1 = pr.mult_inverse[1];
+    S.max_depth = max_depth;
+    S.sample_center = 0;  // the probes' own sampler: HaltonSampler(1, sampleBounds)
+    S.sobol = 0;
+    S.lens_radius = 0;
+    S.diff_scale = diff_scale;
+    return S;
+}
 }  // namespace
 
 int iile_render_probes(iile_scene *sc, int32_t n_probes, const float *pos3, const float *dir3, float *intensity_rgb, float *normals_xyz,
@@ -244,27 +269,8 @@ int iile_render_probes(iile_scene *sc, int32_t n_probes, const float *pos3, cons
         if (stats) *stats = st;
         return IILE_OK;
     }
-    // the probe's film, sampler and depth in place of the frame's
-    DScene S = sc->ds;
+    const DScene S = probe_scene(sc, pr.max_depth, 1.f);  // ScaleDifferentials(1 / sqrt(1 sample per pixel))
     const iile_film_desc &f = pr.film;
-    S.probe_mode = 1;
-    S.xres = f.xres, S.yres = f.yres;
-    S.crop_x0 = f.crop_x0, S.crop_y0 = f.crop_y0, S.crop_x1 = f.crop_x1, S.crop_y1 = f.crop_y1;
-    S.samp_x0 = f.samp_x0, S.samp_y0 = f.samp_y0, S.samp_x1 = f.samp_x1, S.samp_y1 = f.samp_y1;
-    S.filter_rx = f.filter_rx, S.filter_ry = f.filter_ry;
-    S.max_sample_luminance = f.max_sample_luminance;
-    S.filter_wide = 1;
-    S.filter_table = sc->probe_filter_table;
-    S.pixel_offsets = sc->probe_pixel_offsets;
-    S.base_scale0 = pr.base_scales[0], S.base_scale1 = pr.base_scales[1];
-    S.base_exp0 = pr.base_exponents[0], S.base_exp1 = pr.base_exponents[1];
-    S.sample_stride = pr.sample_stride;
-    S.mult_inv0 = pr.mult_inverse[0], S.mult_inv1 = pr.mult_inverse[1];
-    S.max_depth = pr.max_depth;
-    S.sample_center = 0;  // the probes' own sampler: HaltonSampler(1, sampleBounds)
-    S.sobol = 0;
-    S.lens_radius = 0;
-    S.diff_scale = 1.f;  // ScaleDifferentials(1 / sqrt(1 sample per pixel))
     const int need_dims = 5 + 8 * (pr.max_depth + 1) + 2;
     if (S.n_hdims < need_dims) return api_fail(IILE_ERR_ARG, "Halton table covers too few dimensions for the probe depth");
 
@@ -347,6 +353,169 @@ int iile_render_probes(iile_scene *sc, int32_t n_probes, const float *pos3, cons
     st.workspace_bytes = sc->ws_block.cap;
     sc->pb.aux = nullptr;
     if (stats) *stats = st;
+    return IILE_OK;
+}
+
+// ---- IISPT reference mode: many samples per probe pixel, the reference points ------------
+int iile_render_probes_reference(iile_scene *sc, int32_t n_probes, const float *pos3, const float *dir3, const iile_probe_ref_params *prm,
+                                 float *intensity_rgb, float *weight_sum, float *normals_xyz, float *distance, iile_stats *stats) {
+    if (!sc || n_probes < 0 || !pos3 || !dir3 || !prm || !intensity_rgb) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: null argument");
+    if (prm->n_samples < 1) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: n_samples < 1");
+    if (prm->first_sample < 0) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: first_sample < 0");
+    if (prm->max_depth < 1 || prm->max_depth > 14) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: max_depth outside 1 .. 14");
+    if ((normals_xyz == nullptr) != (distance == nullptr))
+        return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: normals_xyz and distance come together or not at all");
+    int rc = ensure_device();
+    if (rc) return rc;
+    const iile_probe_setup &pr = sc->probe;
+    if (pr.hemi_size <= 0 || !sc->probe_pixel_offsets) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: the scene has no probe setup");
+    const int spp_total = prm->spp_total > 0 ? prm->spp_total : prm->n_samples;
+    const DScene S = probe_scene(sc, prm->max_depth, 1.f / std::sqrt(float(spp_total)));
+    const iile_film_desc &f = pr.film;
+    const int need_dims = 5 + 8 * (prm->max_depth + 1) + 2;
+    if (S.n_hdims < need_dims)
+        return api_fail(IILE_ERR_ARG, "Halton table covers " + std::to_string(S.n_hdims) + " dimensions, probe depth " + std::to_string(prm->max_depth) + " needs " +
+                                          std::to_string(need_dims) + " (the table follows the scene's maxdepth)");
+    // GetIndexForSample(k) = the pixel's first index (< sample_stride) + k sample_stride, a 32-bit number on the device
+    if ((uint64_t(prm->first_sample) + uint64_t(prm->n_samples)) * uint64_t(std::max(S.sample_stride, 1)) > 0x100000000ull)
+        return api_fail(IILE_ERR_UNSUPPORTED, "iile_render_probes_reference: sample " + std::to_string(int64_t(prm->first_sample) + prm->n_samples - 1) +
+                                                  " of a probe pixel has a Halton index beyond 32 bits");
+    const int n_ord = probe_film_tiles(S);
+    if (n_ord == 0) return api_fail(IILE_ERR_UNSUPPORTED, "iile_render_probes_reference: the accumulating probe film holds films of at most 1024 pixels");
+    iile_stats st;
+    std::memset(&st, 0, sizeof(st));
+    if (n_probes == 0) {
+        if (stats) *stats = st;
+        return IILE_OK;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(prm->stream);
+    PassDesc P;
+    rc = frame_pass(sc, S, 0, 1, stream, &P);
+    if (rc) return rc;
+    P.probe_mode = 1;
+    P.probe_stx = (f.crop_x1 - f.crop_x0 + 15) / 16;
+    P.probe_tiles = P.probe_stx * ((f.crop_y1 - f.crop_y0 + 15) / 16);
+    const uint32_t per_pixels = uint32_t(f.crop_x1 - f.crop_x0) * uint32_t(f.crop_y1 - f.crop_y0);
+    const uint64_t slots_per_probe = uint64_t(P.probe_tiles) * 256;
+    // One set of launches renders `group` samples of `batch` probes: path id = (probe, pixel, sample of the group), as iile_render_direct
+    // groups passes — one sample of a few probes leaves most of a persistent traversal grid idle. Both are cut from the workspace
+    // budget (and from 2^24 paths: beyond that nothing of a launch's fixed cost is left to spread), never from n_samples.
+    const uint64_t max_paths = std::min<uint64_t>(path_budget(430.0), uint64_t(1) << 24);
+    const int batch = int(std::max<uint64_t>(1, std::min<uint64_t>(uint64_t(n_probes), max_paths / slots_per_probe)));
+    int group = int(std::max<uint64_t>(1, std::min<uint64_t>(uint64_t(prm->n_samples), max_paths / (uint64_t(batch) * slots_per_probe))));
+    if (sc->probe_ref_group_override) group = int(std::min<uint32_t>(sc->probe_ref_group_override, uint32_t(prm->n_samples)));   // iile_test_probe_ref_group
+    const uint64_t batch_paths = uint64_t(batch) * slots_per_probe * uint64_t(group);
+    if (batch_paths > kMaxPassPaths) return api_fail(IILE_ERR_UNSUPPORTED, "iile_render_probes_reference: one set of launches would hold more than 200 000 000 paths");
+
+    std::vector<DProbeCam> cams(static_cast<size_t>(n_probes));
+    for (int i = 0; i < n_probes; ++i)
+        if (!make_probe_camera(pos3 + 3 * size_t(i), dir3 + 3 * size_t(i), &cams[size_t(i)]))
+            return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: degenerate probe direction (probe " + std::to_string(i) + ")");
+
+    LaunchCfg cfg{sc->n_cus, stream, false};
+    rc = ensure_workspace(sc, uint32_t(batch_paths));
+    if (rc) return rc;
+    const bool on_device = prm->outputs_on_device != 0, want_aux = normals_xyz != nullptr;
+    DProbeCam *d_cams = nullptr;
+    float4 *d_acc = nullptr;
+    float *d_int = nullptr, *d_w = nullptr, *d_nrm = nullptr, *d_dist = nullptr;
+    const size_t acc_records = size_t(batch) * size_t(n_ord) * per_pixels;
+    auto layout = [&](Carver c) {
+        d_cams = c.take<DProbeCam>(size_t(batch));
+        sc->pb.aux = c.take<float4>(size_t(batch_paths));
+        d_acc = c.take<float4>(acc_records);
+        if (!on_device) {
+            d_int = c.take<float>(size_t(batch) * per_pixels * 3);
+            d_w = c.take<float>(size_t(batch) * per_pixels);
+            d_nrm = c.take<float>(size_t(batch) * per_pixels * 3);
+            d_dist = c.take<float>(size_t(batch) * per_pixels);
+        }
+        return c.used;
+    };
+    if ((rc = sc->probe_block.reserve(layout(Carver())))) return rc;
+    layout(Carver(sc->probe_block.p));
+    struct AuxGuard {  // (error returns below must not leave the scene pointing into the block)
+        PassBuffers *pb;
+        ~AuxGuard() { pb->aux = nullptr; }
+    } aux_guard{&sc->pb};
+    sc->pb.nray_out = nullptr;
+    sc->events_used = 0;
+    HIP_TRY(hipEventRecord(sc->ev_begin, stream));
+    HIP_TRY(hipMemsetAsync(sc->pb.counters, 0, sizeof(DCounters), stream));
+    for (int first = 0; first < n_probes; first += batch) {
+        const int nb = std::min(batch, n_probes - first);
+        HIP_TRY(hipMemcpyAsync(d_cams, cams.data() + first, size_t(nb) * sizeof(DProbeCam), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(d_acc, 0, size_t(nb) * size_t(n_ord) * per_pixels * sizeof(float4), stream));
+        P.probe_cams = d_cams;
+        P.n_owned_tiles = nb * P.probe_tiles;
+        const size_t px = size_t(nb) * per_pixels, off = size_t(first) * per_pixels;
+        float *o_int = on_device ? intensity_rgb + 3 * off : d_int;
+        float *o_w = weight_sum ? (on_device ? weight_sum + off : d_w) : nullptr;
+        float *o_nrm = want_aux ? (on_device ? normals_xyz + 3 * off : d_nrm) : nullptr, *o_dist = want_aux ? (on_device ? distance + off : d_dist) : nullptr;
+        for (int g0 = 0; g0 < prm->n_samples; g0 += group) {
+            P.k0 = prm->first_sample + g0;
+            P.kc = std::min(group, prm->n_samples - g0);
+            P.n_paths = uint32_t(uint64_t(nb) * slots_per_probe * uint64_t(P.kc));
+            rc = run_pass(sc, S, prm->max_depth, P, cfg, false);
+            if (rc) return rc;
+            // (normals and distances: the first hits of sample first_sample, path 0 of every pixel of the first group)
+            launch_probe_film_add(S, P, sc->pb, nb, d_acc, n_ord, g0 == 0 ? o_nrm : nullptr, g0 == 0 ? o_dist : nullptr, cfg);
+            HIP_TRY(hipGetLastError());
+            st.n_passes++;
+            st.n_paths += uint64_t(nb) * per_pixels * uint64_t(P.kc);
+        }
+        launch_probe_film_resolve(S, P, nb, d_acc, n_ord, o_int, o_w, cfg);
+        HIP_TRY(hipGetLastError());
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(intensity_rgb + 3 * off, d_int, px * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+            if (weight_sum) HIP_TRY(hipMemcpyAsync(weight_sum + off, d_w, px * sizeof(float), hipMemcpyDeviceToHost, stream));
+            if (want_aux) {
+                HIP_TRY(hipMemcpyAsync(normals_xyz + 3 * off, d_nrm, px * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipMemcpyAsync(distance + off, d_dist, px * sizeof(float), hipMemcpyDeviceToHost, stream));
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(stream));   // (the next batch reuses the cameras, the sums and the staging images)
+    }
+    HIP_TRY(hipEventRecord(sc->ev_end, stream));
+    DCounters c;
+    HIP_TRY(hipMemcpyAsync(&c, sc->pb.counters, sizeof(c), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, sc->ev_begin, sc->ev_end));
+    st.ms_total = ms;
+    st.mis_rays_traced = c.mis_traced, st.ext_rays_traced = c.ext_traced;
+    st.workspace_bytes = sc->ws_block.cap;
+    if (stats) *stats = st;
+    return IILE_OK;
+}
+
+int iile_test_probe_ref_group(iile_scene *sc, uint32_t samples_per_group) {
+    if (!sc) return api_fail(IILE_ERR_ARG, "iile_test_probe_ref_group: null scene");
+    sc->probe_ref_group_override = samples_per_group;
+    return IILE_OK;
+}
+
+int iile_reference_points(iile_scene *sc, int32_t n, const float *pfilm2, uint8_t *valid, float *pos3, float *dir3) {
+    if (!sc || n < 0 || !pfilm2 || !valid || !pos3 || !dir3) return api_fail(IILE_ERR_ARG, "iile_reference_points: bad argument");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (n == 0) return IILE_OK;
+    DevBuf<float> dpf, dpos, ddir;
+    DevBuf<float4> dro, drd, dh;
+    DevBuf<uint8_t> dv;
+    const size_t m = size_t(n);
+    if ((rc = dpf.put(pfilm2, 2 * m)) || (rc = dro.alloc(m)) || (rc = drd.alloc(m)) || (rc = dh.alloc(2 * m)) || (rc = dv.alloc(m)) || (rc = dpos.alloc(3 * m)) ||
+        (rc = ddir.alloc(3 * m)))
+        return rc;
+    DScene S = sc->ds;
+    S.diff_scale = 1.f;  // ray.ScaleDifferentials(1), iispt.cpp:517
+    const LaunchCfg cfg{sc->n_cus, nullptr, false};
+    launch_reference_rays(S, n, dpf.p, dro.p, drd.p, cfg);
+    launch_trace(S, n, dro.p, drd.p, dh.p, 0, nullptr, sc->spill, cfg);
+    launch_reference_points(S, n, dro.p, drd.p, dh.p, dv.p, dpos.p, ddir.p, cfg);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if ((rc = dv.get(valid, m)) || (rc = dpos.get(pos3, 3 * m)) || (rc = ddir.get(dir3, 3 * m))) return rc;
     return IILE_OK;
 }
 

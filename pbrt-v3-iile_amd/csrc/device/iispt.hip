@@ -252,6 +252,42 @@ __global__ __launch_bounds__(kIisptBlock) __attribute__((amdgpu_waves_per_eu(4))
     }
 }
 
+// The reference mode's points (IISPTIntegrator::render_reference / Li_reference, iispt.cpp:509-520, 650-672): the camera ray through
+// pFilm with the lens sample of a default CameraSample, and — from its closest hit, whatever the surface scatters: no specular chain
+// is followed, unlike find_intersection — the aux ray along the surface normal turned against the ray. The closest hits in between
+// are k_trace's (launch_trace).
+__global__ __launch_bounds__(kIisptBlock) void k_reference_rays(DScene S, int n, const float *pfilm2, float4 *ro, float4 *rd) {
+    const int i = blockIdx.x * kIisptBlock + threadIdx.x;
+    if (i >= n) return;
+    F3 o, d;
+    float tmax;
+    camera_ray(S, pfilm2[2 * i], pfilm2[2 * i + 1], 0.f, 0.f, &o, &d, &tmax);
+    ro[i] = make_float4(o.x, o.y, o.z, 0.f);
+    rd[i] = make_float4(d.x, d.y, d.z, tmax);
+}
+__global__ __launch_bounds__(kIisptBlock) void k_reference_points(DScene S, int n, const float4 *ro, const float4 *rd, const float4 *hits, uint8_t *valid,
+                                                                  float *pos3, float *dir3) {
+    const int i = blockIdx.x * kIisptBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 o4 = ro[i], d4 = rd[i], h0 = hits[2 * i], h1 = hits[2 * i + 1];
+    const int prim = int(f2b(h0.x));
+    F3 o = F3{0, 0, 0}, d = F3{0, 0, 0};
+    if (prim >= 0) {
+        const F3 ray_o = F3{o4.x, o4.y, o4.z}, ray_d = F3{d4.x, d4.y, d4.z};
+        const float4 v0 = S.tri_verts[3 * size_t(prim)], v1 = S.tri_verts[3 * size_t(prim) + 1], v2 = S.tri_verts[3 * size_t(prim) + 2];
+        const uint32_t flags = f2b(v0.w);
+        Isect is;
+        if (flags & 1u)
+            shape_hit_interaction<true>(S, S.prim_shape[prim], ray_o, ray_d, &is);
+        else
+            triangle_interaction(S, prim, flags, F3{v0.x, v0.y, v0.z}, F3{v1.x, v1.y, v1.z}, F3{v2.x, v2.y, v2.z}, ray_d, h1.x, h1.y, h1.z, &is);
+        iispt_aux_ray(is, ray_d, &o, &d);
+    }
+    valid[i] = prim >= 0 ? 1 : 0;
+    pos3[3 * i] = o.x, pos3[3 * i + 1] = o.y, pos3[3 * i + 2] = o.z;
+    dir3[3 * i] = d.x, dir3[3 * i + 1] = d.y, dir3[3 * i + 2] = d.z;
+}
+
 namespace {
 // IntensityFilm::get_camera_coord_jacobian (film/intensityfilm.cpp:60-66) on the predicted image of a hemi point:
 // [y][x][3] with row 0 the top scanline (film->get(x, height - 1 - y)); jac[y] = sin(pi * y / hemi) (host table)
@@ -465,6 +501,14 @@ int launch_iispt_first_hits(const DScene &S, const IisptJob *jobs, int n_jobs, i
 }
 void launch_iispt_hemi_out(const DScene &S, const IisptJob *jobs, int n_jobs, int max_hemi, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_iispt_hemi_out, job_grid(max_hemi, n_jobs, cfg), dim3(kIisptBlock), 0, cfg.stream, S, jobs);
+}
+void launch_reference_rays(const DScene &S, int n, const float *pfilm2, float4 *ro, float4 *rd, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_reference_rays, dim3(unsigned((n + kIisptBlock - 1) / kIisptBlock)), dim3(kIisptBlock), 0, cfg.stream, S, n, pfilm2, ro, rd);
+}
+void launch_reference_points(const DScene &S, int n, const float4 *ro, const float4 *rd, const float4 *hits, uint8_t *valid, float *pos3, float *dir3,
+                             const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_reference_points, dim3(unsigned((n + kIisptBlock - 1) / kIisptBlock)), dim3(kIisptBlock), 0, cfg.stream, S, n, ro, rd, hits, valid,
+                       pos3, dir3);
 }
 void launch_iispt_gather(const DScene &S, const IisptJob *jobs, int n_jobs, int max_pixels, const float *jac, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_iispt_gather, job_grid(max_pixels, n_jobs, cfg), dim3(kIisptBlock), 0, cfg.stream, S, jobs, jac);

@@ -154,6 +154,12 @@ void launch_film_gather(const DScene &S, const PassDesc &P, const FilmBuffers &F
 // the probe pass's film store + gather + finish in one kernel; false (nothing launched): the probe film is too large for it
 bool launch_probe_film(const DScene &S, const PassDesc &P, const PassBuffers &B, int n_probes, float *intensity, float *normals, float *distance,
                        const LaunchCfg &cfg);
+// The accumulating probe film (kernels.hip): probe_film_tiles = the tile sums a probe pixel keeps (0: the probe film is too large for the
+// accumulating film); acc holds n_probes x that x pixels records, zeroed before the first add
+int probe_film_tiles(const DScene &S);
+void launch_probe_film_add(const DScene &S, const PassDesc &P, const PassBuffers &B, int n_probes, float4 *acc, int n_ord, float *normals, float *distance,
+                           const LaunchCfg &cfg);
+void launch_probe_film_resolve(const DScene &S, const PassDesc &P, int n_probes, float4 *acc, int n_ord, float *intensity, float *weight_sum, const LaunchCfg &cfg);
 void launch_direct_generate(const DScene &S, const PassDesc &P, const PassBuffers &B, const LaunchCfg &cfg);
 void launch_direct_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int depth, uint32_t max_rays, const LaunchCfg &cfg);
 void launch_direct_tree(const DScene &S, const PassDesc &P, const PassBuffers &B, double *film_rgbw, const LaunchCfg &cfg);
@@ -193,6 +199,10 @@ struct IisptJob {
 // between its rounds, and once more before it returns the IILE_ERR_HIP of a call that failed
 int launch_iispt_first_hits(const DScene &S, const IisptJob *jobs, int n_jobs, int max_items, uint32_t *n_active, int *spill, const LaunchCfg &cfg);
 void launch_iispt_hemi_out(const DScene &S, const IisptJob *jobs, int n_jobs, int max_hemi, const LaunchCfg &cfg);
+// the reference mode's points (iispt.hip): camera rays through n film positions; the aux rays on their closest hits (hits: launch_trace's records)
+void launch_reference_rays(const DScene &S, int n, const float *pfilm2, float4 *ro, float4 *rd, const LaunchCfg &cfg);
+void launch_reference_points(const DScene &S, int n, const float4 *ro, const float4 *rd, const float4 *hits, uint8_t *valid, float *pos3, float *dir3,
+                             const LaunchCfg &cfg);
 void launch_iispt_gather(const DScene &S, const IisptJob *jobs, int n_jobs, int max_pixels, const float *jac, const LaunchCfg &cfg);
 void launch_iispt_film_add(const int4 *rects, const uint32_t *first, int n_tasks, int max_pixels, const float4 *out, double *film, int film_w, hipStream_t stream);
 void launch_iispt_film_merge(const double *a, const double *b, float *rgb, long long n, hipStream_t stream);

@@ -243,8 +243,15 @@ __global__ __launch_bounds__(kBlock) void k_probe_finish(DScene S, PassDesc P, P
 // One film pixel of the gather: the sum over the tiles whose FilmTile holds (x, y), in tile index order, of the samples
 // FilmTile::AddSample would have added to it, in pixel then sample order. rec1(qx, qy, row): the record {film position, radiance} of
 // sample pixel (qx, qy) when there is one sample per pixel; the several-samples form reads F directly.
-template <typename Rec1>
-DEV float4 film_gather_pixel(const DScene &S, const PassDesc &P, const FilmBuffers &F, const float *s_table, int x, int y, int n_samples, Rec1 rec1) {
+// sums(ordinal): the running {r, g, b, w} of the pixel's tile number `ordinal` (counted row by row over the tiles its samples can come
+// from) in an accumulating film — loaded before the tile's samples are added, stored after; the plain gather starts every tile at zero.
+struct NoTileSums {
+    DEV void load(int, float *, float *, float *, float *) const {}
+    DEV void store(int, float, float, float, float) const {}
+};
+template <typename Rec1, typename Sums = NoTileSums>
+DEV float4 film_gather_pixel(const DScene &S, const PassDesc &P, const FilmBuffers &F, const float *s_table, int x, int y, int n_samples, Rec1 rec1,
+                             Sums sums = Sums()) {
     const float rx = S.filter_rx, ry = S.filter_ry;
     const float inv_rx = 1 / rx, inv_ry = 1 / ry;  // Filter::invRadius
     // sample pixels that can reach (x, y): |q + u - 0.5 - x| <= r with u in [0, 1), i.e. x - r - 0.5 < q <= x + r + 0.5
@@ -270,6 +277,8 @@ DEV float4 film_gather_pixel(const DScene &S, const PassDesc &P, const FilmBuffe
                 const int fy0 = max(int(ceilf(float(sy0) - 0.5f - ry)), S.crop_y0), fy1 = min(int(floorf(float(sy1) - 0.5f + ry)) + 1, S.crop_y1);
                 if (x < fx0 || x >= fx1 || y < fy0 || y >= fy1) continue;
                 float r = 0, g = 0, b = 0, w = 0;
+                const int ordinal = (ty - ty0) * (tx1 - tx0 + 1) + (tx - tx0);
+                sums.load(ordinal, &r, &g, &b, &w);
                 // FilmTile::AddSample's support test and table lookup for this pixel (film.h:159-188)
                 auto add_sample = [&](float2 pf, float4 L) {
                     const float dxf = pf.x - 0.5f, dyf = pf.y - 0.5f;
@@ -319,6 +328,7 @@ DEV float4 film_gather_pixel(const DScene &S, const PassDesc &P, const FilmBuffe
                         }
                     }
                 }
+                sums.store(ordinal, r, g, b, w);
                 add_xyz(&out, r, g, b, w);
             }
     }
@@ -390,6 +400,95 @@ __global__ __launch_bounds__(kBlock) void k_probe_film(DScene S, PassDesc P, Pas
             normals[3 * i + 2] = a.z;
             distance[i] = a.w;
         }
+    }
+}
+
+// The accumulating probe film (iile_render_probes_reference: many samples per probe pixel behind the probe's filter). Per probe pixel
+// and per tile its samples can come from, {sum of w L, sum of w} in HBM: acc[(probe * n_ord + ordinal) * per + pixel]. k_probe_film_add
+// adds the P.kc samples of one set of launches to it: a block takes a probe and, sample after sample, keeps that sample's film — guarded
+// radiance, film position — in LDS as k_probe_film does, and every thread adds it to its pixels' sums through film_gather_pixel. A sum
+// grows in the order (sample, then pixel row by row), one addition at a time on the stored value, so it is the same number however the
+// samples are cut into sets of launches; with one sample it is k_probe_film's. normals / distance (null: not wanted): the first hits of
+// sample P.k0, as k_probe_film picks them.
+struct ProbeTileSums {
+    float4 *acc;     // the pixel's record of tile 0
+    size_t stride;   // records between two tiles of a pixel
+    bool write;
+    DEV void load(int ordinal, float *r, float *g, float *b, float *w) const {
+        const float4 v = acc[size_t(ordinal) * stride];
+        *r = v.x, *g = v.y, *b = v.z, *w = v.w;
+    }
+    DEV void store(int ordinal, float r, float g, float b, float w) const {
+        if (write) acc[size_t(ordinal) * stride] = make_float4(r, g, b, w);
+    }
+};
+__global__ __launch_bounds__(kBlock) void k_probe_film_add(DScene S, PassDesc P, PassBuffers B, int n_probes, float4 *acc, int n_ord, float *normals,
+                                                           float *distance) {
+    __shared__ float s_table[256];
+    __shared__ float2 s_pf[kProbeFilmMax];
+    __shared__ float4 s_L[kProbeFilmMax];
+    for (int j = threadIdx.x; j < 256; j += kBlock) s_table[j] = S.filter_table[j];
+    const int fw = S.crop_x1 - S.crop_x0, fh = S.crop_y1 - S.crop_y0;
+    const int per = fw * fh;
+    FilmBuffers none = {};
+    for (uint32_t probe = blockIdx.x; probe < uint32_t(n_probes); probe += gridDim.x) {
+        for (int kk = 0; kk < P.kc; ++kk) {
+            __syncthreads();   // (the table; the previous sample's gathers)
+            for (int j = threadIdx.x; j < per; j += kBlock) {
+                const int x = S.crop_x0 + j % fw, y = S.crop_y0 + j / fw;
+                const float4 L4 = B.L[probe_record(S, P, probe, x, y) * size_t(P.kc) + size_t(kk)];
+                const F3 L = guard_radiance(S, F3{L4.x, L4.y, L4.z});
+                const uint32_t idx = sample_index(S, x, y, uint32_t(P.k0) + uint32_t(kk));
+                s_L[j] = make_float4(L.x, L.y, L.z, 0.f);
+                s_pf[j] = make_float2(float(x) + sample_dimension(S, idx, 0, x, y), float(y) + sample_dimension(S, idx, 1, x, y));
+            }
+            __syncthreads();
+            for (int j = threadIdx.x; j < per; j += kBlock) {
+                const int x = S.crop_x0 + j % fw, y = S.crop_y0 + j / fw;
+                const ProbeTileSums sums{acc + size_t(probe) * size_t(n_ord) * size_t(per) + size_t(j), size_t(per), true};
+                film_gather_pixel(S, P, none, s_table, x, y, 1, [&](int qx, int qy, size_t, float2 *pf, float4 *L) {
+                    const int at = (qy - S.crop_y0) * fw + (qx - S.crop_x0);
+                    *pf = s_pf[at];
+                    *L = s_L[at];
+                }, sums);
+            }
+        }
+        if (normals)
+            for (int j = threadIdx.x; j < per; j += kBlock) {
+                const int x = S.crop_x0 + j % fw, y = S.crop_y0 + j / fw;
+                const size_t i = size_t(probe) * size_t(per) + size_t(j);
+                const float4 a = B.aux[probe_record(S, P, probe, x, y) * size_t(P.kc)];
+                normals[3 * i] = a.x;
+                normals[3 * i + 1] = a.y;
+                normals[3 * i + 2] = a.z;
+                distance[i] = a.w;
+            }
+    }
+}
+// ... and its end: the tiles' sums of a pixel merged as Film::MergeFilmTile merges FilmTiles (a gather that adds no sample), then
+// Film::to_rgb_array as k_probe_finish; weight_sum (null: not wanted): the pixel's filterWeightSum.
+__global__ __launch_bounds__(kBlock) void k_probe_film_resolve(DScene S, PassDesc P, int n_probes, float4 *acc, int n_ord, float *intensity, float *weight_sum) {
+    __shared__ float s_table[256];
+    for (int j = threadIdx.x; j < 256; j += kBlock) s_table[j] = S.filter_table[j];
+    __syncthreads();
+    const int fw = S.crop_x1 - S.crop_x0, fh = S.crop_y1 - S.crop_y0;
+    const uint32_t per = uint32_t(fw) * uint32_t(fh), n = per * uint32_t(n_probes);
+    FilmBuffers none = {};
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const uint32_t probe = i / per, loc = i % per;
+        const int x = S.crop_x0 + int(loc % uint32_t(fw)), y = S.crop_y0 + int(loc / uint32_t(fw));
+        const ProbeTileSums sums{acc + size_t(probe) * size_t(n_ord) * size_t(per) + size_t(loc), size_t(per), false};
+        const float4 px = film_gather_pixel(S, P, none, s_table, x, y, 0, [](int, int, size_t, float2 *, float4 *) {}, sums);
+        float rgb[3];
+        rgb[0] = 3.240479f * px.x - 1.537150f * px.y - 0.498535f * px.z;  // XYZToRGB, spectrum.h:56-60
+        rgb[1] = -0.969256f * px.x + 1.875991f * px.y + 0.041556f * px.z;
+        rgb[2] = 0.055648f * px.x - 0.204043f * px.y + 1.057311f * px.z;
+        if (px.w != 0) {
+            const float inv_wt = 1.f / px.w;
+            for (int c = 0; c < 3; ++c) rgb[c] = mx(0.f, rgb[c] * inv_wt);
+        }
+        for (int c = 0; c < 3; ++c) intensity[3 * size_t(i) + c] = (rgb[c] + 0.f) * 1.f;
+        if (weight_sum) weight_sum[i] = px.w;
     }
 }
 
@@ -568,6 +667,22 @@ bool launch_probe_film(const DScene &S, const PassDesc &P, const PassBuffers &B,
     hipLaunchKernelGGL(k_probe_film, dim3(unsigned(std::min(n_probes, cfg.n_cus * 8))), dim3(kBlock), 0, cfg.stream, S, P, B, n_probes, intensity, normals,
                        distance);
     return true;
+}
+int probe_film_tiles(const DScene &S) {
+    const uint32_t per = uint32_t(S.crop_x1 - S.crop_x0) * uint32_t(S.crop_y1 - S.crop_y0);
+    if (per > uint32_t(kProbeFilmMax)) return 0;
+    // a pixel gathers from 2 ceil(r + 0.5) + 1 sample pixels along an axis (film_gather_pixel), n pixels lie in at most (n - 2) / 16 + 2 tiles
+    const int ax = (2 * int(ceilf(S.filter_rx + 0.5f)) - 1) / kTile + 2, ay = (2 * int(ceilf(S.filter_ry + 0.5f)) - 1) / kTile + 2;
+    return ax * ay;
+}
+void launch_probe_film_add(const DScene &S, const PassDesc &P, const PassBuffers &B, int n_probes, float4 *acc, int n_ord, float *normals, float *distance,
+                           const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_probe_film_add, dim3(unsigned(std::min(n_probes, cfg.n_cus * 8))), dim3(kBlock), 0, cfg.stream, S, P, B, n_probes, acc, n_ord, normals,
+                       distance);
+}
+void launch_probe_film_resolve(const DScene &S, const PassDesc &P, int n_probes, float4 *acc, int n_ord, float *intensity, float *weight_sum, const LaunchCfg &cfg) {
+    const uint32_t n = uint32_t(S.crop_x1 - S.crop_x0) * uint32_t(S.crop_y1 - S.crop_y0) * uint32_t(n_probes);
+    hipLaunchKernelGGL(k_probe_film_resolve, dim3(grid_blocks(n, cfg.n_cus, 8)), dim3(kBlock), 0, cfg.stream, S, P, n_probes, acc, n_ord, intensity, weight_sum);
 }
 void launch_film_gather(const DScene &S, const PassDesc &P, const FilmBuffers &F, int n_samples, const LaunchCfg &cfg) {
     const uint32_t n = uint32_t(S.crop_x1 - S.crop_x0) * uint32_t(S.crop_y1 - S.crop_y0) *
