@@ -340,6 +340,11 @@ int iile_bvh_pack_probe(int32_t n_nodes, const iile_bvh_node *nodes, int32_t n_i
 /* How this build packs the refs of a four-wide record: 0 = the plain ref and an axes word of its own; 2 = ref << 2 | split
  * axis (of the node, its first child, its second child) — one vector load less per interior step. */
 int32_t iile_wide_ref_shift(void);
+/* The traversal limits this build was compiled with, for tests that place their cases on them: out3 = {IILE_LDS_STACK: stack levels
+ * a lane keeps in LDS before the oldest is evicted to HBM; IILE_TOP_RECORDS: four-wide records of the tree's top the kernels keep in
+ * LDS; the deepest tree iile_scene_create accepts, as interior nodes on the longest path from the root to a leaf (64, the entries of
+ * the reference's own nodesToVisit, bvh.cpp:670 — a deeper tree is IILE_ERR_UNSUPPORTED: a lane's stack might not hold it)}. */
+void iile_traversal_limits(int32_t *out3);
 /* Light::Sample_Li of delta light `light` (point, spot, distant, projection, goniometric: iile_light_is_delta; any other is
  * IILE_ERR_ARG) at n points p3, each an Interaction without a surface: out7 = {wi.xyz, Li.rgb, pdf} per point. */
 int iile_light_sample_li(iile_scene *scene, int32_t light, int32_t n, const float *p3, float *out7);

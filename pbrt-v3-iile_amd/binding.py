@@ -196,7 +196,7 @@ GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iil
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
                "iile_iispt_film_add", "iile_iispt_film_merge",
                "iile_iispt_hemi_points", "iile_iispt_gather", "iile_iispt_hemi_points_batch", "iile_iispt_gather_batch", "iile_bvh_build_hlbvh", "iile_bvh_pack_probe", "iile_render_direct",
-               "iile_wide_ref_shift", "iile_render_status", "iile_test_patch_capacity", "iile_iispt_net_create", "iile_iispt_net_load", "iile_iispt_net_forward", "iile_iispt_net_predict", "iile_iispt_net_destroy"]
+               "iile_wide_ref_shift", "iile_traversal_limits", "iile_render_status", "iile_test_patch_capacity", "iile_iispt_net_create", "iile_iispt_net_load", "iile_iispt_net_forward", "iile_iispt_net_predict", "iile_iispt_net_destroy"]
 DIST_SYMBOLS = ["iile_dist_unique_id", "iile_dist_create", "iile_dist_create_deadline", "iile_dist_abort", "iile_dist_wait", "iile_dist_destroy", "iile_dist_rank", "iile_dist_size", "iile_dist_ranks_seen",
                 "iile_dist_film_reduce", "iile_dist_monitor_reduce", "iile_dist_barrier", "iile_dist_sum_u64", "iile_dist_max_f64",
                 "iile_dist_rendezvous_file", "iile_dist_rendezvous_file_token", "iile_dist_rendezvous_done", "iile_dist_all_ok",
@@ -326,6 +326,8 @@ def gpu_lib():
         lib.iile_bvh_build_hlbvh.argtypes = [c_i32, c_vp, c_i32, c_vp, ctypes.POINTER(c_i32), c_vp, ctypes.POINTER(BvhBuildStats)]
         lib.iile_bvh_pack_probe.argtypes = [c_i32, c_vp, c_i32, c_vp, c_vp, ctypes.POINTER(c_i32)]
         lib.iile_render_status.argtypes = [c_vp, c_vp]
+        lib.iile_traversal_limits.argtypes = [ctypes.POINTER(c_i32)]
+        lib.iile_traversal_limits.restype = None
         lib.iile_test_patch_capacity.argtypes = [c_vp, c_u32]
         lib.iile_iispt_net_create.argtypes = [ctypes.POINTER(NetWeights), ctypes.POINTER(c_vp)]
         lib.iile_iispt_net_load.argtypes = [ctypes.c_char_p, ctypes.POINTER(c_vp)]
@@ -1018,6 +1020,14 @@ def bvh_pack_probe(nodes):
     if rc != 0:
         raise RuntimeError(f"iile_bvh_pack_probe failed ({rc}): {gpu_lib().iile_last_error().decode()}")
     return wide[:ni], wide4[:ni], bool(nested.value)
+
+
+def traversal_limits():
+    """iile_traversal_limits: what this build's traversal kernels were compiled with, as a dict: lds_stack (IILE_LDS_STACK),
+    top_records (IILE_TOP_RECORDS), max_bvh_depth (the deepest tree iile_scene_create accepts). Needs no GPU."""
+    out = (c_i32 * 3)()
+    gpu_lib().iile_traversal_limits(out)
+    return {"lds_stack": int(out[0]), "top_records": int(out[1]), "max_bvh_depth": int(out[2])}
 
 
 def trig_probe(x):

@@ -99,6 +99,20 @@ int interior_nodes(const iile_scene_desc &d) {
     return int(std::count_if(d.nodes, d.nodes + std::max(d.n_nodes, 0), [](const iile_bvh_node &nd) { return nd.nprims == 0; }));
 }
 
+// Interior nodes on the longest path from the root to a leaf of a flattened tree that passed check_bvh_nodes (a parent lies
+// before its children: one pass)
+int bvh_depth(const iile_bvh_node *nodes, int n_nodes) {
+    std::vector<int> level(size_t(std::max(n_nodes, 0)), 0);
+    int deepest = 0;
+    for (int i = 0; i < n_nodes; ++i) {
+        if (nodes[i].nprims > 0)
+            deepest = std::max(deepest, level[i]);
+        else
+            level[i + 1] = level[nodes[i].offset] = level[i] + 1;
+    }
+    return deepest;
+}
+
 // Every refusal of iile_scene_create, in the order it has always made them, before any device call: a malformed
 // descriptor is refused on a machine without a GPU too. The builders below assume a descriptor that passed.
 int check_scene_desc(const iile_scene_desc &d) {
@@ -149,6 +163,12 @@ int check_scene_desc(const iile_scene_desc &d) {
     // the references between the tables
     int n_interior = 0;
     if (const int rc = check_bvh_nodes(d.nodes, d.n_nodes, d.n_prims, "", &n_interior)) return rc;
+    // a lane's traversal stack holds a tree of traversal_limits().max_bvh_depth levels (dpath.h: kMaxBvhDepth); a deeper one could
+    // write past the lane's HBM column into its neighbours'
+    const int depth = bvh_depth(d.nodes, d.n_nodes), max_depth = traversal_limits().max_bvh_depth;
+    if (depth > max_depth)
+        return api_fail(IILE_ERR_UNSUPPORTED, "BVH depth " + std::to_string(depth) + " exceeds the traversal stack's limit of " +
+                                                  std::to_string(max_depth) + " levels");
     for (int i = 0; i < d.n_prims; ++i)
         if ((d.prim_flags[i] & IILE_PRIM_SPHERE) && d.prim_light[i] >= 0 && d.lights[d.prim_light[i]].sphere != d.prim_shape[i])
             return api_fail(IILE_ERR_ARG, "light / sphere cross reference is inconsistent");

@@ -1032,6 +1032,10 @@ extern "C" int iile_bvh_build_hlbvh(int32_t n_prims, const float *bounds6, int32
 
 // Test probe for pack_wide_records: the records of a flattened tree handed over by the host.
 extern "C" int32_t iile_wide_ref_shift(void) { return kRefShift; }
+extern "C" void iile_traversal_limits(int32_t *out3) {
+    const TraversalLimits l = traversal_limits();
+    out3[0] = l.lds_stack, out3[1] = l.top_records, out3[2] = l.max_bvh_depth;
+}
 
 extern "C" int iile_bvh_pack_probe(int32_t n_nodes, const iile_bvh_node *nodes, int32_t n_interior, float *wide16, float *wide4_32,
                                    int32_t *nested) {

@@ -916,6 +916,18 @@ constexpr int kLdsStackDepth = IILE_LDS_STACK;  // measured max depth on killero
 // The reference's stack holds 64 binary entries (bvh.cpp:670); a four-wide step defers up to
 // three slots where the binary walk defers one child, so the same tree needs up to 1.5x that.
 constexpr int kSpillStackDepth = 128 - IILE_LDS_STACK;
+// The deepest tree a lane's stack is sure to hold; iile_scene_create refuses a deeper one (api_scene.hip). Depth = interior nodes
+// on the longest path from the root to a leaf: what the reference's nodesToVisit[64] holds at most, since its walk defers one
+// child per interior node it enters — and it does not check either (bvh.cpp:670), so 64 is also where the reference ends.
+// Here a binary step (instrumented kernels, rays with an infinite 1/d) defers one entry per level; a four-wide step at node P
+// descends to a grandchild, two levels, and defers at most the three other slots (entering a leaf child, one level, it defers at
+// most two and the descent ends). A path of `depth` levels therefore holds at most 3 * ceil(depth / 2) entries: 96 for 64, of
+// the kLdsStackDepth + kSpillStackDepth = 128 a lane's ring and HBM column hold together, and of the 255 Trav::sp counts.
+constexpr int kMaxBvhDepth = 64;
+constexpr int stack_levels_needed(int depth) { return 3 * ((depth + 1) / 2); }
+static_assert(stack_levels_needed(kMaxBvhDepth) <= IILE_LDS_STACK + kSpillStackDepth && kMaxBvhDepth <= IILE_LDS_STACK + kSpillStackDepth,
+              "a tree of kMaxBvhDepth levels must fit a lane's LDS ring plus its HBM column");
+static_assert(IILE_LDS_STACK + kSpillStackDepth < 256, "Trav::sp counts the stack's levels in 8 bits");
 constexpr int kStackWordsPerWave = 2 * kLdsStackDepth * 64;  // ref plane + tMin plane
 
 struct TraceStats {

@@ -479,6 +479,7 @@ constexpr int kMaxTraverseBlocksPerCu = 8;  // spill columns are sized for this 
 uint32_t max_traversal_threads(int n_cus) {
     return uint32_t(n_cus) * kMaxTraverseBlocksPerCu * kBlock * kSpillStackDepth * 2;  // (ref, tMin) per level
 }
+TraversalLimits traversal_limits() { return {kLdsStackDepth, kMaxTop, kMaxBvhDepth}; }
 uint32_t queue_capacity(uint32_t n_paths, int n_cus) {
     // every wavefront that appends can leave < 64 slots per kOutBlock it fills plus one
     // partly filled block behind

@@ -262,3 +262,63 @@ def test_sobol_resolution(binding, tmp_path):
     assert desc.create() == (ERR_ARG, "iile_sobol: bad dimension count / resolution, or sample indices beyond 32 bits")
     sb.resolution, sb.log2_resolution = 16, 4
     assert desc.create() == (ERR_ARG, "iile_sobol: resolution smaller than the sample bounds")
+
+
+def _chain_scene(binding, tmp_path, depth):
+    """A scene whose tree is a left-leaning chain of `depth` interior nodes over depth + 1 unit boxes, handed in through the
+    bvh_build hook: node i's first child is node i + 1, its second the leaf 2 * depth - i."""
+    proto = ctypes.CFUNCTYPE(ctypes.c_int, c_i32, c_vp, c_i32, c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp)
+    n_prims = depth + 1
+
+    def chain(n, bounds6, max_prims, nodes_out, n_nodes, order, stats):
+        assert n == n_prims
+        b = np.ctypeslib.as_array(ctypes.cast(bounds6, ctypes.POINTER(c_f32)), (n, 6))
+        nodes = ctypes.cast(nodes_out, ctypes.POINTER(BvhNode))
+        for i in range(depth):      # interior node i holds primitives 0 .. depth - i
+            nodes[i].bmin[:] = b[:depth - i + 1, :3].min(0).tolist()
+            nodes[i].bmax[:] = b[:depth - i + 1, 3:].max(0).tolist()
+            nodes[i].offset, nodes[i].nprims, nodes[i].axis, nodes[i].pad = 2 * depth - i, 0, 0, 0
+        for j in range(n):          # leaf of primitive j: node `depth` for j = 0, else node depth + j
+            leaf = nodes[depth + j]
+            leaf.bmin[:], leaf.bmax[:] = b[j, :3].tolist(), b[j, 3:].tolist()
+            leaf.offset, leaf.nprims, leaf.axis, leaf.pad = j, 1, 0, 0
+            order[j] = j
+        n_nodes[0] = 2 * depth + 1
+        return 0
+
+    tris = " ".join("%d 0 0  %d 1 0  %d 1 1" % (j, j + 1, j + 1) for j in range(n_prims))   # one triangle per unit box along x
+    text = f"""LookAt 0 0 -5  0 0 0  0 1 0
+Camera "perspective" "float fov" [60]
+Film "image" "integer xresolution" [16] "integer yresolution" [16] "string filename" "chain.exr"
+Sampler "halton" "integer pixelsamples" [1]
+Accelerator "bvh" "string splitmethod" ["hlbvh"] "integer maxnodeprims" [1]
+WorldBegin
+Material "matte"
+Shape "trianglemesh" "point P" [ {tris} ] "integer indices" [ {" ".join(str(i) for i in range(3 * n_prims))} ]
+WorldEnd
+"""
+    path = tmp_path / f"chain{depth}.pbrt"
+    path.write_text(text)
+    host = binding.HostScene(path=str(path), bvh_on_device=proto(chain))
+    assert host.info["n_nodes"] == 2 * depth + 1 and host.info["n_interior_nodes"] == depth
+    return host
+
+
+def test_bvh_deeper_than_the_traversal_stack(binding, tmp_path):
+    """A tree one level deeper than the traversal stack is sure to hold (iile_traversal_limits: the reference's own 64) is refused,
+    naming the depth; nothing is ever traced on it."""
+    limit = binding.traversal_limits()["max_bvh_depth"]
+    desc = Desc(binding, _chain_scene(binding, tmp_path, limit + 1))
+    assert desc.create() == (ERR_UNSUPPORTED, f"BVH depth {limit + 1} exceeds the traversal stack's limit of {limit} levels")
+
+
+def test_bvh_exactly_as_deep_as_the_limit_is_accepted(binding, tmp_path):
+    """A chain of exactly the limit's depth passes every refusal (the first one left is a later check's, as in
+    test_material_texture_indices_are_checked_as_clamped); it is not traced either."""
+    limit = binding.traversal_limits()["max_bvh_depth"]
+    desc = Desc(binding, _chain_scene(binding, tmp_path, limit))
+    desc.d.sobol.enabled = 1  # (a Sobol' table of no dimensions: refused last)
+    assert desc.create()[1].startswith("iile_sobol: bad dimension count")
+    if binding.device_count() > 0:
+        desc.d.sobol.enabled = 0
+        assert desc.create()[0] == 0
