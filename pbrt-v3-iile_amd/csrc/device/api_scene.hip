@@ -163,7 +163,7 @@ int check_scene_desc(const iile_scene_desc &d) {
     // the references between the tables
     int n_interior = 0;
     if (const int rc = check_bvh_nodes(d.nodes, d.n_nodes, d.n_prims, "", &n_interior)) return rc;
-    // a lane's traversal stack holds a tree of traversal_limits().max_bvh_depth levels (dpath.h: kMaxBvhDepth); a deeper one could
+    // a lane's traversal stack holds a tree of traversal_limits().max_bvh_depth levels (dtrav.h: kMaxBvhDepth); a deeper one could
     // write past the lane's HBM column into its neighbours'
     const int depth = bvh_depth(d.nodes, d.n_nodes), max_depth = traversal_limits().max_bvh_depth;
     if (depth > max_depth)
@@ -292,7 +292,7 @@ int scene_alloc(iile_scene *sc, size_t bytes, T **out, const char *what) {
 // The builders: each fills its part of sc->ds (uploading into sc->allocs) from a checked descriptor, in this order.
 // BVH: the depth-first LinearBVHNode array (bvh.cpp:640-658) is re-packed on the device (bvh_build.hip,
 // pack_wide_records) into the two-wide records {children[0] box, children[1] box, refs, axis} of the instrumented kernels
-// and the four-wide records of dpath.h trav_interior4. A reference is the interior record index, or ~firstPrimitive for a
+// and the four-wide records of dtrav.h trav_interior4. A reference is the interior record index, or ~firstPrimitive for a
 // leaf child.
 int build_bvh(iile_scene *sc, const iile_scene_desc &d) {
     DScene &S = sc->ds;
@@ -326,7 +326,7 @@ int build_bvh(iile_scene *sc, const iile_scene_desc &d) {
     return IILE_OK;
 }
 
-// The top of the four-wide tree, breadth first, for the traversal kernels' LDS copies (dpath.h, load_wide4): the
+// The top of the four-wide tree, breadth first, for the traversal kernels' LDS copies (dtrav.h, load_wide4): the
 // records are read back once, the references among the chosen ones become kTopFlag | slot, each copy keeps its own
 // record index (the binary fallback step needs it) in the word behind its axes.
 int build_top4(iile_scene *sc, const iile_scene_desc &d) {
@@ -416,7 +416,7 @@ int build_prims(iile_scene *sc, const iile_scene_desc &d) {
     if (!rc) rc = upload(sc, norms.data(), norms.size(), &S.tri_norms);
     if (!rc) rc = upload(sc, uvs.data(), uvs.size(), &S.tri_uv);
     if (rc) return rc;
-    // a quadric primitive's shape is ~(its quadric index) on the device: the sign tells the shape's kind (dpath.h)
+    // a quadric primitive's shape is ~(its quadric index) on the device: the sign tells the shape's kind (dtrav.h)
     std::vector<int> shape(d.prim_shape, d.prim_shape + n);
     sc->prim_is_shape.assign(n, 0);
     for (size_t i = 0; i < n; ++i) {

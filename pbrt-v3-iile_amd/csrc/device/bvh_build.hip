@@ -790,7 +790,7 @@ __global__ __launch_bounds__(kBB) void k_pack_wide(int n, const iile_bvh_node *n
         w[1] = make_float4(a.bmax[1], a.bmax[2], b.bmin[0], b.bmin[1]);
         w[2] = make_float4(b.bmin[2], b.bmax[0], b.bmax[1], b.bmax[2]);
         w[3] = make_float4(__int_as_float(ra), __int_as_float(rb), __int_as_float(int(nd.axis)), 0.f);
-        // a child's box must lie inside its parent's for the four-wide step to skip the children (dpath.h trav_interior4)
+        // a child's box must lie inside its parent's for the four-wide step to skip the children (dtrav.h trav_interior4)
         bool nested = true;
         for (int c = 0; c < 3; ++c)
             nested = nested && a.bmin[c] >= nd.bmin[c] && a.bmax[c] <= nd.bmax[c] && b.bmin[c] >= nd.bmin[c] && b.bmax[c] <= nd.bmax[c];

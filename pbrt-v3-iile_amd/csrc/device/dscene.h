@@ -124,7 +124,7 @@ struct DProbeCam {
 #ifndef IILE_TOP_RECORDS
 #define IILE_TOP_RECORDS 21  // levels 0..2 of the four-wide tree (1 + 4 + 16); 85 = levels 0..3
 #endif
-constexpr int kMaxTop = IILE_TOP_RECORDS;  // records of the tree's top kept in LDS by the traversal kernels (dpath.h)
+constexpr int kMaxTop = IILE_TOP_RECORDS;  // records of the tree's top kept in LDS by the traversal kernels (dtrav.h)
 // The three split axes of a four-wide record ride in the low two bits of its first three refs (ref << kRefShift | axis) instead of
 // a word of their own, so that k_extend's interior step issues 7 vector loads per lane instead of 8 — on the deep-tree room the
 // traversal kernels retire vector-memory lane-loads at the rate the L1 path allows at all (tools/vmem_calib.hip,
@@ -161,7 +161,7 @@ struct DScene {
     float root_box[6];        // bounds of the root node (min.xyz, max.xyz)
     int root_ref;             // >= 0: wide record; < 0: ~first primitive of a single-leaf tree
     // The top levels of the four-wide tree once more (breadth first, at most kMaxTop records of 8 float4): every block of a
-    // traversal kernel keeps a copy in LDS, and references between them are kTopFlag | slot (dpath.h, load_wide4).
+    // traversal kernel keeps a copy in LDS, and references between them are kTopFlag | slot (dtrav.h, load_wide4).
     const float4 *top4;
     int n_top;
     int root_ref_top;         // root_ref, or kTopFlag | 0 when the root record is among them

@@ -212,7 +212,7 @@ void launch_trace(const DScene &S, int n, const float4 *ro, const float4 *rd, fl
                   DCounters *counters, int *spill, const LaunchCfg &cfg);
 // number of ints of the HBM spill array: kSpillStackDepth x the largest traversal grid
 uint32_t max_traversal_threads(int n_cus);
-// what this build's traversal kernels were compiled with (dpath.h, dscene.h): stack levels per lane in LDS, records of the
+// what this build's traversal kernels were compiled with (dtrav.h, dscene.h): stack levels per lane in LDS, records of the
 // tree's top in LDS, and the deepest tree (interior nodes on a root-to-leaf path) the stack columns hold
 struct TraversalLimits {
     int lds_stack, top_records, max_bvh_depth;

@@ -12,16 +12,7 @@ namespace iile {
 // itself (what k_generate would have written and this kernel read back: 64 B per path)
 template <bool COUNT, bool ALPHA, bool GEN>
 __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_extend(DScene S, PassDesc P, PassBuffers B, int bounce) {
-    __shared__ int lds_stack[kTravWavesPerBlock][2 * kLdsStackDepth][64];
-    __shared__ __attribute__((aligned(16))) char lds_top[COUNT ? 16 : kMaxTop * kTopStride];
-    StackRef sr{(lds_int *)&lds_stack[threadIdx.x >> 6][0][threadIdx.x & 63], B.spill, blockIdx.x * kTravBlock + threadIdx.x, gridDim.x * kTravBlock};
-    sr.root = S.root_ref;
-    if (!COUNT && S.n_top > 0) {  // the instrumented build walks the binary records: no four-wide steps, no top
-        stage_top_records(S, (lds_char *)lds_top, int(threadIdx.x), kTravBlock);
-        __syncthreads();
-        sr.top = (lds_char *)lds_top;
-        sr.root = S.root_ref_top;
-    }
+    const StackRef sr = trav_block_begin<COUNT, kTravBlock>(S, B.spill);
     const uint32_t count = B.counts[kCntRay + bounce];
     uint32_t *head = &B.counts[kCntExtHead + bounce];
     const float4 *ro = B.ray_o[bounce & 1], *rd = B.ray_d[bounce & 1];
@@ -35,57 +26,25 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_extend(DScene S
         warm_plane(ro, first, count);
         warm_plane(rd, first, count);
     };
-    Trav t;
-    t.have = false;
-    t.cur = 0;
-    t.sp = 0;
-    t.hit_prim = -1;
+    Trav t;  // (an idle lane)
     bool active = false;
     uint32_t slot = 0;
     float4 gen_d = make_float4(0, 0, 1, 0);  // GEN: the ray direction (the sphere test reads it back)
-#ifdef IILE_TRAV_ITERSTATS
     // diagnostic build only (tools/trav_stamps.py iterstats): what the wavefronts of bounces >= 1 look like at each vote —
     // [0] interior votes, [1] lanes stepping in them, [2] lanes waiting at a leaf meanwhile, [3] leaf votes, [4] lanes stepping,
     // [5] lanes waiting at an interior record meanwhile, [6] idle lanes (no ray) summed over all votes, [7] refills
-    unsigned long long iter_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define ITER_STAT(kind, n_go, n_wait)                                            \
-    do {                                                                         \
-        iter_stat[3 * (kind)] += 1;                                              \
-        iter_stat[3 * (kind) + 1] += uint32_t(n_go);                             \
-        iter_stat[3 * (kind) + 2] += uint32_t(n_wait);                           \
-        iter_stat[6] += uint32_t(64 - (n_go) - (n_wait));                        \
-    } while (0)
-#else
-#define ITER_STAT(kind, n_go, n_wait) \
-    do {                              \
-    } while (0)
-#endif
-#ifdef IILE_TRAV_STAMPS
+    DiagSums<IILE_SWITCH(IILE_TRAV_ITERSTATS) && !COUNT && !GEN, 8> iter_stat;
     // diagnostic build only (tools/trav_stamps.py): wave cycles per section of the loop, summed per wavefront and added to
     // DCounters::path_length: the camera-ray build [0] refill + ray generation, [1] interior steps, [2] leaf steps,
     // [3] finish + queue append; the other bounces the same in [4..7]
-    unsigned long long stamp_sum[4] = {0, 0, 0, 0};
-    unsigned long long stamp_t = __builtin_amdgcn_s_memtime();
-#define TRAV_STAMP(i)                                                   \
-    do {                                                                \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
-        stamp_sum[i] += now_ - stamp_t;                                 \
-        stamp_t = now_;                                                 \
-    } while (0)
-#else
-#define TRAV_STAMP(i) \
-    do {              \
-    } while (0)
-#endif
+    DiagSums<IILE_SWITCH(IILE_TRAV_STAMPS) && !COUNT, 4> stamps;
     while (true) {
-        TRAV_STAMP(3);
+        stamps.mark(3);
         const unsigned long long idle_mask = __ballot(!active);
         // (the camera-ray build makes its rays here, some 400 instructions each: it waits for more idle lanes than the others)
         if (refill_due(idle_mask, feed, GEN ? IILE_REFILL_IDLE_GEN : kRefillIdle, GEN ? IILE_REFILL_IDLE_GEN_SLOW : IILE_REFILL_IDLE_SLOW)) {
             uint32_t s_new;
-#ifdef IILE_TRAV_ITERSTATS
-            iter_stat[7] += 1;
-#endif
+            iter_stat.add(7, 1);
             if (feed_take(feed, head, count, !active, &s_new, warm)) {
                 slot = s_new;
                 if (GEN) {
@@ -129,26 +88,20 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_extend(DScene S
                 }
             }
         }
-        TRAV_STAMP(0);
+        stamps.mark(0);
         if (__ballot(active) == 0) {
             if (feed.exhausted) break;
             continue;
         }
         // one step per iteration for the whole wavefront, interior or leaf, whichever has more
         // lanes waiting (25.9 ms vs 34.6 ms for strict while-while on the 1080p/64spp step)
-        {
-            const bool wi = active && t.have && t.cur >= 0;
-            const bool wl = active && t.have && t.cur < 0;
-            const int n_int = __popcll(__ballot(wi)), n_leaf = __popcll(__ballot(wl));
-            if (n_int > 0 && n_int * kVoteNum >= n_leaf * kVoteDen) {
-                if (wi) trav_step<COUNT>(S, t, sr, &st);
-                ITER_STAT(0, n_int, n_leaf);
-                TRAV_STAMP(1);
-            } else if (n_leaf > 0) {
-                ITER_STAT(1, n_leaf, n_int);
-                if (wl) trav_leaf<COUNT, ALPHA>(S, t, sr, &st, false, GEN ? &gen_d : &rd[slot]);
-                TRAV_STAMP(2);
-            }
+        const WaveStep ws = trav_wave_step<COUNT, ALPHA, false>(S, active, t, sr, &st, false, GEN ? &gen_d : &rd[slot]);
+        if (ws.kind >= 0) {
+            iter_stat.add(3 * ws.kind, 1);
+            iter_stat.add(3 * ws.kind + 1, uint32_t(ws.n_go));
+            iter_stat.add(3 * ws.kind + 2, uint32_t(ws.n_wait));
+            iter_stat.add(6, uint32_t(64 - ws.n_go - ws.n_wait));
+            stamps.mark(1 + ws.kind);
         }
         const bool fin = active && !t.have;
         const bool is_hit = fin && t.hit_prim >= 0;
@@ -163,14 +116,8 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_extend(DScene S
         if (is_hit) B.shade_q[pos] = slot | (uint32_t(t.hit_prim >> kHitClassShift) & 7u) << kSlotBits;
     }
     out_flush(shade_out, pad_shade);
-#ifdef IILE_TRAV_STAMPS
-    if (!COUNT && (threadIdx.x & 63) == 0)
-        for (int i = 0; i < 4; ++i) atomicAdd(&B.counters->path_length[(GEN ? 0 : 4) + i], stamp_sum[i]);
-#endif
-#ifdef IILE_TRAV_ITERSTATS
-    if (!COUNT && !GEN && (threadIdx.x & 63) == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(&B.counters->path_length[i], iter_stat[i]);
-#endif
+    stamps.flush(B.counters, GEN ? 0 : 4);
+    iter_stat.flush(B.counters, 0);
     flush_counter(&B.counters->ext_traced, n_rays);  // every build: the uninstrumented pass leaves out rays that cannot matter
     if (COUNT) {
         flush_counter(&B.counters->closest_rays, n_rays);
@@ -198,26 +145,13 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_extend(DScene S
 
 template <bool COUNT, bool ALPHA>
 __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_shadow(DScene S, PassBuffers B, int bounce, uint32_t plane) {
-    __shared__ int lds_stack[kTravWavesPerBlock][2 * kLdsStackDepth][64];
-    __shared__ __attribute__((aligned(16))) char lds_top[COUNT ? 16 : kMaxTop * kTopStride];
-    StackRef sr{(lds_int *)&lds_stack[threadIdx.x >> 6][0][threadIdx.x & 63], B.spill, blockIdx.x * kTravBlock + threadIdx.x, gridDim.x * kTravBlock};
-    sr.root = S.root_ref;
-    if (!COUNT && S.n_top > 0) {  // the instrumented build walks the binary records: no four-wide steps, no top
-        stage_top_records(S, (lds_char *)lds_top, int(threadIdx.x), kTravBlock);
-        __syncthreads();
-        sr.top = (lds_char *)lds_top;
-        sr.root = S.root_ref_top;
-    }
+    const StackRef sr = trav_block_begin<COUNT, kTravBlock>(S, B.spill);
     const uint32_t count = B.counts[kCntNee + bounce];
     uint32_t *head = &B.counts[kCntConHead + bounce];
     TraceStats st = {0, 0, 0, 0};
     unsigned long long n_shadow = 0, n_zero = 0;
     WaveFeed feed{0, 0, count == 0};
-    Trav t;
-    t.have = false;
-    t.cur = 0;
-    t.sp = 0;
-    t.hit_prim = -1;
+    Trav t;  // (an idle lane)
     bool active = false, occluded = false;
     uint32_t e = 0, pid = 0;
     // The record's two possible outcomes, L + beta * Ld with and without the light sample, are
@@ -227,23 +161,10 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_shadow(DScene S
     // (L itself is only *consumed* at the store, so its load — the one scattered access of the
     // record — overlaps the ray's first traversal steps instead of holding up the refill.)
     F3 L_old = F3{0, 0, 0}, add_unoccluded = F3{0, 0, 0}, add_occluded = F3{0, 0, 0};
-#ifdef IILE_SHADOW_STAMPS
     // diagnostic build only (tools/trav_stamps.py shadow): as in k_extend — [0] refill, [1] interior steps, [2] leaf steps, [3] finish
-    unsigned long long stamp_sum[4] = {0, 0, 0, 0};
-    unsigned long long stamp_t = __builtin_amdgcn_s_memtime();
-#define SHADOW_STAMP(i)                                                 \
-    do {                                                                \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
-        stamp_sum[i] += now_ - stamp_t;                                 \
-        stamp_t = now_;                                                 \
-    } while (0)
-#else
-#define SHADOW_STAMP(i) \
-    do {                \
-    } while (0)
-#endif
+    DiagSums<IILE_SWITCH(IILE_SHADOW_STAMPS) && !COUNT, 4> stamps;
     while (true) {
-        SHADOW_STAMP(3);
+        stamps.mark(3);
         const unsigned long long idle_mask = __ballot(!active);
         if (refill_due(idle_mask, feed, kRefillIdle)) {
             uint32_t e_new;
@@ -261,11 +182,7 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_shadow(DScene S
                     // ray carries beta * (A / lightPdf) ready made (k_shade) and no throughput plane.
                     const float4 n0 = B.nee[e], a4 = B.nee[4 * size_t(plane) + e];
                     pid = f2b(a4.w);
-#ifdef IILE_SHADOW_DIAG_NO_L_READ   // timing only (wrong film): what the scattered 16-byte read of L costs this kernel (profiles/r06_ab_shadow_L_read.txt)
-                    const float4 L4 = make_float4(0, 0, 0, 0);
-#else
                     const float4 L4 = B.L[pid];
-#endif
                     const bool has_shadow = (flags & NEE_HAS_SHADOW) != 0;
                     if (flags & NEE_HAS_MIS) {
                         const float4 be = B.nee[6 * size_t(plane) + e];
@@ -302,7 +219,7 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_shadow(DScene S
                 }
             }
         }
-        SHADOW_STAMP(0);
+        stamps.mark(0);
         if (__ballot(active) == 0) {
             if (feed.exhausted) break;
             continue;
@@ -310,18 +227,9 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_shadow(DScene S
         // Shadow rays end at their first hit, so lanes leave at very different times: one
         // step per iteration, interior or leaf, whichever keeps more lanes busy
         // (17.9 ms vs 22.1 ms for strict while-while on the 1080p/64spp step).
-        {
-            const bool wi = active && t.have && t.cur >= 0;
-            const bool wl = active && t.have && t.cur < 0;
-            const int n_int = __popcll(__ballot(wi)), n_leaf = __popcll(__ballot(wl));
-            if (n_int > 0 && n_int * kVoteNum >= n_leaf * kVoteDen) {
-                if (wi) trav_step<COUNT, true>(S, t, sr, &st);
-                SHADOW_STAMP(1);
-            } else if (n_leaf > 0) {
-                if (wl && trav_leaf<COUNT, ALPHA>(S, t, sr, &st, true, &B.nee[plane + e])) occluded = true;
-                SHADOW_STAMP(2);
-            }
-        }
+        const WaveStep ws = trav_wave_step<COUNT, ALPHA, true>(S, active, t, sr, &st, true, &B.nee[plane + e]);
+        if (ws.hit) occluded = true;
+        if (ws.kind >= 0) stamps.mark(1 + ws.kind);
         if (active && !t.have) {
             const F3 add = occluded ? add_occluded : add_unoccluded;
             const F3 Ln = L_old + add;  // store only: nothing is loaded here
@@ -332,10 +240,7 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_shadow(DScene S
             active = false;
         }
     }
-#ifdef IILE_SHADOW_STAMPS
-    if (!COUNT && (threadIdx.x & 63) == 0)
-        for (int i = 0; i < 4; ++i) atomicAdd(&B.counters->path_length[i], stamp_sum[i]);
-#endif
+    stamps.flush(B.counters, 0);
     if (COUNT) {
         flush_counter(&B.counters->shadow_rays, n_shadow);
         flush_counter(&B.counters->zero_radiance, n_zero);
@@ -351,27 +256,14 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_shadow(DScene S
 // four-wide records are walked unordered, as k_shadow walks them
 template <bool COUNT, bool ALPHA, bool ANYORDER = false>
 __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_mis(DScene S, PassBuffers B, int bounce, uint32_t plane) {
-    __shared__ int lds_stack[kTravWavesPerBlock][2 * kLdsStackDepth][64];
-    __shared__ __attribute__((aligned(16))) char lds_top[COUNT ? 16 : kMaxTop * kTopStride];
-    StackRef sr{(lds_int *)&lds_stack[threadIdx.x >> 6][0][threadIdx.x & 63], B.spill, blockIdx.x * kTravBlock + threadIdx.x, gridDim.x * kTravBlock};
-    sr.root = S.root_ref;
-    if (!COUNT && S.n_top > 0) {  // the instrumented build walks the binary records: no four-wide steps, no top
-        stage_top_records(S, (lds_char *)lds_top, int(threadIdx.x), kTravBlock);
-        __syncthreads();
-        sr.top = (lds_char *)lds_top;
-        sr.root = S.root_ref_top;
-    }
+    const StackRef sr = trav_block_begin<COUNT, kTravBlock>(S, B.spill);
     // the dense queue of MIS rays k_shade wrote beside the NEE records: (o, record) in plane 2, (d, light) in plane 3
     const uint32_t count = B.counts[kCntMis + bounce];
     uint32_t *head = &B.counts[kCntMisHead + bounce];
     TraceStats st = {0, 0, 0, 0};
     unsigned long long n_closest = 0, n_traced = 0;
     WaveFeed feed{0, 0, count == 0};
-    Trav t;
-    t.have = false;
-    t.cur = 0;
-    t.sp = 0;
-    t.hit_prim = -1;
+    Trav t;  // (an idle lane)
     bool active = false, first_hit_ends = false;
     uint32_t q = 0, e = 0;
     while (true) {
@@ -406,16 +298,7 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_mis(DScene S, P
             if (feed.exhausted) break;
             continue;
         }
-        {
-            const bool wi = active && t.have && t.cur >= 0;
-            const bool wl = active && t.have && t.cur < 0;
-            const int n_int = __popcll(__ballot(wi)), n_leaf = __popcll(__ballot(wl));
-            if (n_int > 0 && n_int * kVoteNum >= n_leaf * kVoteDen) {
-                if (wi) trav_step<COUNT, ANYORDER>(S, t, sr, &st);
-            } else if (n_leaf > 0) {
-                if (wl) trav_leaf<COUNT, ALPHA>(S, t, sr, &st, false, &B.nee[3 * size_t(plane) + q]);
-            }
-        }
+        trav_wave_step<COUNT, ALPHA, ANYORDER>(S, active, t, sr, &st, false, &B.nee[3 * size_t(plane) + q]);
         if (first_hit_ends && active && t.hit_prim >= 0) t.have = false;
         if (active && !t.have) {
             // store only: (area light index + 1) of the primitive the MIS ray ended on, 0 for none
@@ -490,68 +373,35 @@ static dim3 trav_grid(uint32_t n, const LaunchCfg &cfg) {
     const int per_cu256 = cfg.trav_blocks_per_cu > 0 ? cfg.trav_blocks_per_cu : kTraverseBlocksPerCu;
     return dim3(grid_blocks(n, cfg.n_cus, std::max(1, per_cu256 * kBlock / kTravBlock), kTravBlock));
 }
+// (count_stats: the instrumented build, always with ALPHA; rare_prims: the ALPHA build)
 void launch_extend(const DScene &S, const PassDesc &P, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg) {
-    const dim3 grid = trav_grid(max_rays, cfg);
+    using K = void (*)(DScene, PassDesc, PassBuffers, int);
+    static constexpr K plain[2][2] = {{k_extend<false, false, false>, k_extend<false, false, true>},  // [ALPHA][GEN]
+                                      {k_extend<false, true, false>, k_extend<false, true, true>}};
     const bool gen = bounce == 0 && P.gen_fused && !cfg.count_stats;
-    if (cfg.count_stats)
-        hipLaunchKernelGGL((k_extend<true, true, false>), grid, dim3(kTravBlock), 0, cfg.stream, S, P, B, bounce);
-    else if (S.rare_prims) {
-        if (gen)
-            hipLaunchKernelGGL((k_extend<false, true, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, P, B, bounce);
-        else
-            hipLaunchKernelGGL((k_extend<false, true, false>), grid, dim3(kTravBlock), 0, cfg.stream, S, P, B, bounce);
-    } else {
-        if (gen)
-            hipLaunchKernelGGL((k_extend<false, false, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, P, B, bounce);
-        else
-            hipLaunchKernelGGL((k_extend<false, false, false>), grid, dim3(kTravBlock), 0, cfg.stream, S, P, B, bounce);
-    }
+    const K k = cfg.count_stats ? k_extend<true, true, false> : plain[S.rare_prims ? 1 : 0][gen];
+    hipLaunchKernelGGL(k, trav_grid(max_rays, cfg), dim3(kTravBlock), 0, cfg.stream, S, P, B, bounce);
 }
 void launch_shadow(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg) {
-    const dim3 grid = trav_grid(max_rays, cfg);
-    if (cfg.count_stats)
-        hipLaunchKernelGGL((k_shadow<true, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-    else
-        {
-        if (S.rare_prims)
-            hipLaunchKernelGGL((k_shadow<false, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-        else
-            hipLaunchKernelGGL((k_shadow<false, false>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-    }
+    using K = void (*)(DScene, PassBuffers, int, uint32_t);
+    const K k = cfg.count_stats ? k_shadow<true, true> : S.rare_prims ? k_shadow<false, true> : k_shadow<false, false>;
+    hipLaunchKernelGGL(k, trav_grid(max_rays, cfg), dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
 }
 void launch_mis(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg) {
-    const dim3 grid = trav_grid(max_rays, cfg);
-    if (cfg.count_stats)
-        hipLaunchKernelGGL((k_mis<true, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-    else
-        {
-        if (S.all_lights_infinite) {
-            if (S.rare_prims)
-                hipLaunchKernelGGL((k_mis<false, true, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-            else
-                hipLaunchKernelGGL((k_mis<false, false, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-        } else if (S.rare_prims)
-            hipLaunchKernelGGL((k_mis<false, true>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-        else
-            hipLaunchKernelGGL((k_mis<false, false>), grid, dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
-    }
+    using K = void (*)(DScene, PassBuffers, int, uint32_t);
+    static constexpr K plain[2][2] = {{k_mis<false, false, false>, k_mis<false, false, true>},  // [ALPHA][ANYORDER]
+                                      {k_mis<false, true, false>, k_mis<false, true, true>}};
+    const K k = cfg.count_stats ? k_mis<true, true, false> : plain[S.rare_prims ? 1 : 0][S.all_lights_infinite ? 1 : 0];
+    hipLaunchKernelGGL(k, trav_grid(max_rays, cfg), dim3(kTravBlock), 0, cfg.stream, S, B, bounce, B.queue_cap);
 }
 void launch_trace(const DScene &S, int n, const float4 *ro, const float4 *rd, float4 *hits, int any_hit,
                   DCounters *counters, int *spill, const LaunchCfg &cfg) {
-    const dim3 grid(grid_blocks(uint32_t(n), cfg.n_cus, kTraverseBlocksPerCu));
     // count_stats selects the instrumented traversal (binary steps) or the one the render
     // kernels run uninstrumented (four-wide steps)
-    if (any_hit) {
-        if (cfg.count_stats)
-            hipLaunchKernelGGL((k_trace<true, true>), grid, dim3(kBlock), 0, cfg.stream, S, n, ro, rd, hits, counters, spill);
-        else
-            hipLaunchKernelGGL((k_trace<true, false>), grid, dim3(kBlock), 0, cfg.stream, S, n, ro, rd, hits, counters, spill);
-    } else {
-        if (cfg.count_stats)
-            hipLaunchKernelGGL((k_trace<false, true>), grid, dim3(kBlock), 0, cfg.stream, S, n, ro, rd, hits, counters, spill);
-        else
-            hipLaunchKernelGGL((k_trace<false, false>), grid, dim3(kBlock), 0, cfg.stream, S, n, ro, rd, hits, counters, spill);
-    }
+    using K = void (*)(DScene, int, const float4 *, const float4 *, float4 *, DCounters *, int *);
+    static constexpr K tab[2][2] = {{k_trace<false, false>, k_trace<false, true>}, {k_trace<true, false>, k_trace<true, true>}};  // [ANY][COUNT]
+    const dim3 grid(grid_blocks(uint32_t(n), cfg.n_cus, kTraverseBlocksPerCu));
+    hipLaunchKernelGGL(tab[any_hit ? 1 : 0][cfg.count_stats ? 1 : 0], grid, dim3(kBlock), 0, cfg.stream, S, n, ro, rd, hits, counters, spill);
 }
 
 }  // namespace iile

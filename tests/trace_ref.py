@@ -195,7 +195,7 @@ def any_disagreements(tr, hit):
 # ---- a float64 walk of a flattened tree that records the stack, as the device keeps it -------------------------------------
 def stack_profile(nodes, tri_p, o, d, tmax, lds_levels):
     """BVHAccel::Intersect's walk (bvh.cpp:662-700) in float64, all rays in step, with the stack kept as the instrumented device walk
-    keeps it: one entry per interior node entered, the newest `lds_levels` entries in a ring and older ones evicted (dpath.h:
+    keeps it: one entry per interior node entered, the newest `lds_levels` entries in a ring and older ones evicted (dtrav.h:
     stack_push, trav_pop). Per ray: peak (the largest stack size), evictions, hbm_pops (pops that had to come back from evicted
     levels), again (evictions after such a pop), and t (the closest hit, inf on a miss)."""
     P = np.asarray(tri_p, np.float64).reshape(-1, 9)

@@ -1,5 +1,5 @@
 """Where a k_shade wavefront's cycles go: the diagnostic build (-DIILE_SHADE_STAMPS: s_memtime stamps between the sections of a
-round, tools/build_variant.sh stamps "kernels_shade api" "-DIILE_SHADE_STAMPS") renders the bench frame once and prints the
+round, tools/build_variant.sh stamps "kernels_shade api_render" "-DIILE_SHADE_STAMPS") renders the bench frame once and prints the
 per-section share of the waves' cycles. The stamps themselves cost ~10 %: shares, not absolute times.
 usage: IILE_GPU_LIB=pbrt-v3-iile_amd/lib/variants/libiile_gpu_stamps.so python tools/shade_stamps.py"""
 import json

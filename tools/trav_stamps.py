@@ -1,5 +1,5 @@
 """Where a k_extend wavefront's cycles go: the diagnostic build (-DIILE_TRAV_STAMPS: s_memtime stamps between the sections of the
-persistent loop; tools/build_variant.sh tstamps "kernels_trav api" "-DIILE_TRAV_STAMPS") renders the bench frame once and prints the
+persistent loop; tools/build_variant.sh tstamps "kernels_trav api_render" "-DIILE_TRAV_STAMPS") renders the bench frame once and prints the
 per-section share of the waves' cycles, for the camera-ray build (bounce 0) and for the later bounces. Shares, not absolute times.
 usage: IILE_GPU_LIB=pbrt-v3-iile_amd/lib/variants/libiile_gpu_tstamps.so python tools/trav_stamps.py [killeroo|boxroom] [shadow]
 (shadow: the build made with -DIILE_SHADOW_STAMPS instead, k_shadow's sections in the first four counters)"""
@@ -28,7 +28,7 @@ gpu.render()
 _, st = gpu.render(want_stats=True, time_kernels=2)
 cyc = [int(x) for x in st["path_length"]]
 if "iterstats" in sys.argv[1:]:
-    # the build made with -DIILE_TRAV_ITERSTATS: k_extend's votes at bounces >= 1 (kernels_trav.hip, ITER_STAT)
+    # the build made with -DIILE_TRAV_ITERSTATS: k_extend's votes at bounces >= 1 (kernels_trav.hip, iter_stat)
     iv, il, ilw, lv, ll, lw, idle, refills = cyc
     votes = max(1, iv + lv)
     print(json.dumps({
