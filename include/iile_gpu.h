@@ -164,6 +164,9 @@ int iile_bsdf_sample(iile_scene *scene, int32_t n, int32_t mat, const float *wo3
  * as where a bump map or a mesh's "normal N" tilts it away from the surface. */
 int iile_bsdf_eval_ng(iile_scene *scene, int32_t n, int32_t mat, const float *ng3, const float *wo3, const float *wi3, float *out4);
 int iile_bsdf_sample_ng(iile_scene *scene, int32_t n, int32_t mat, const float *ng3, const float *wo3, const float *u2, float *out7);
+/* BSDF::Sample_f with the specular lobes allowed (type = BSDF_ALL), as the path's bounce samples it: out: 9 floats
+ * {wi.xyz, f.rgb, pdf, sampled_specular, sampled_transmission}, the two flags 0 or 1. */
+int iile_bsdf_sample_specular(iile_scene *scene, int32_t n, int32_t mat, const float *wo3, const float *u2, float *out9);
 /* The IISPT probe pass: for each of n probes, what iisptrenderrunner.cpp:316-346 obtains from
  * CreateHemisphericCamera(hemi, hemi, pos, dir) + IISPTdIntegrator::RenderView + get_intensity_film /
  * get_normal_film / get_distance_film (src/integrators/iispt_d.cpp:66-470, src/cameras/hemispheric.cpp) — the three

@@ -110,6 +110,10 @@ int oracle_bsdf_eval_ng(const iile_scene_desc *scene, int trig_mode, int mat, co
                         float *f3, float *pdf);
 int oracle_bsdf_sample_ng(const iile_scene_desc *scene, int trig_mode, int mat, const float *ng3, const float *wo3, const float *u2,
                           float *wi3, float *f3, float *pdf);
+/* Sample_f with the specular lobes allowed (type = BSDF_ALL) for n (wo, u) pairs: out9n holds {wi(3), f(3), pdf, sampled_specular,
+ * sampled_transmission} per pair, the two flags as 0 or 1 */
+int oracle_bsdf_sample_specular(const iile_scene_desc *scene, int trig_mode, int mat, int n, const float *wo3n, const float *u2n,
+                                float *out9n);
 /* n samples / pdf evaluations for one outgoing direction (chi-square test of src/tests/bsdfs.cpp) */
 int oracle_bsdf_sample_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
                               const float *u2n, float *wi3n, float *pdfn);

@@ -3831,6 +3831,28 @@ int oracle_bsdf_sample(const iile_scene_desc *scene, int trig_mode, int mat, con
                        float *pdf) {
     return oracle_bsdf_sample_ng(scene, trig_mode, mat, nullptr, wo3, u2, wi3, f3, pdf);
 }
+int oracle_bsdf_sample_specular(const iile_scene_desc *scene, int trig_mode, int mat, int n, const float *wo3n, const float *u2n,
+                                float *out9n) {
+    if (int rc = check_material_type(*scene, mat)) return rc;
+    Counters c;
+    Oracle orc(*scene, trig_mode, &c);
+    Oracle::Bsdf b = local_bsdf(orc, scene, mat, nullptr);
+    for (int i = 0; i < n; ++i) {
+        V3 wo(wo3n[3 * i], wo3n[3 * i + 1], wo3n[3 * i + 2]), wi(0, 0, 0);
+        float p = 0;
+        bool spec = false, trans = false;
+        Rgb f = orc.bsdf_sample_f(b, wo, &wi, u2n + 2 * i, &p, true, &spec, &trans);
+        float *o = out9n + 9 * size_t(i);
+        for (int k = 0; k < 3; ++k) {
+            o[k] = wi[k];
+            o[3 + k] = f.c[k];
+        }
+        o[6] = p;
+        o[7] = spec ? 1.f : 0.f;
+        o[8] = trans ? 1.f : 0.f;
+    }
+    return 0;
+}
 int oracle_bsdf_sample_batch(const iile_scene_desc *scene, int trig_mode, int mat, const float *wo3, int n,
                               const float *u2n, float *wi3n, float *pdfn) {
     if (int rc = check_material_type(*scene, mat)) return rc;

@@ -190,7 +190,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
-               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_render_probes",
+               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_bsdf_sample_specular", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_render_probes",
                "iile_render_probes_reference", "iile_test_probe_ref_group", "iile_reference_points",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
@@ -318,6 +318,7 @@ def gpu_lib():
         lib.iile_bsdf_sample.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_bsdf_eval_ng.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_bsdf_sample_ng.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
+        lib.iile_bsdf_sample_specular.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_trig_probe.argtypes = [c_i32, c_vp, c_vp]
         lib.iile_iispt_hemi_points.argtypes = [c_vp, ctypes.POINTER(IisptTask), c_vp, c_vp, c_vp]
         lib.iile_iispt_gather.argtypes = [c_vp, ctypes.POINTER(IisptTask), c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32]
@@ -890,6 +891,14 @@ class GpuScene:
         out = np.empty((len(wo), 7), np.float32)
         self._check(gpu_lib().iile_bsdf_sample_ng(self._s, len(wo), mat, ng.ctypes.data, wo.ctypes.data, u.ctypes.data, out.ctypes.data),
                     "iile_bsdf_sample_ng")
+        return out
+
+    def bsdf_sample_specular(self, mat, wo, u):
+        """bsdf_sample with the specular lobes allowed: {wi (3), f (3), pdf, sampled_specular, sampled_transmission} per (wo, u)."""
+        wo, u = _f32(wo), _f32(u)
+        out = np.empty((len(wo), 9), np.float32)
+        self._check(gpu_lib().iile_bsdf_sample_specular(self._s, len(wo), mat, wo.ctypes.data, u.ctypes.data, out.ctypes.data),
+                    "iile_bsdf_sample_specular")
         return out
 
     def close(self):

@@ -140,6 +140,10 @@ int iile_bsdf_sample_ng(iile_scene *sc, int32_t n, int32_t mat, const float *ng3
     return bsdf_probe(sc, n, mat, wo3, u2, 2, 1, out7, 7, ng3);
 }
 
+int iile_bsdf_sample_specular(iile_scene *sc, int32_t n, int32_t mat, const float *wo3, const float *u2, float *out9) {
+    return bsdf_probe(sc, n, mat, wo3, u2, 2, 2, out9, 9);
+}
+
 int iile_light_sample_li(iile_scene *sc, int32_t light, int32_t n, const float *p3, float *out7) {
     if (!sc || n < 0 || !p3 || !out7 || light < 0 || light >= sc->ds.n_lights)
         return api_fail(IILE_ERR_ARG, "iile_light_sample_li: bad argument");

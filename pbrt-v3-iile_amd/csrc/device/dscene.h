@@ -36,7 +36,7 @@ struct DQuadric {
 };
 enum { kMatMatte = 0, kMatPlastic = 1, kMatUber = 2, kMatMirror = 3, kMatGlass = 4, kMatMetal = 5, kMatSubstrate = 6,
        kMatTranslucent = 8 };  // = IILE_MAT_* (checked in api_scene.hip)
-// (16-byte aligned, and the fields every hit reads first: (type, kd) and (ks, alpha) are one float4 each, see make_bsdf)
+// (16-byte aligned, and the fields every hit reads first: (type, kd) and (ks, alpha) are one float4 each, see make_bsdf in dbsdf.h)
 struct alignas(16) DMaterial {
     int type;
     float kd[3];

@@ -587,7 +587,8 @@ __global__ void k_camera(DScene S, int n, const float *pfilm, const float *plens
     d[3 * i + 2] = rd.z;
 }
 // BSDF in a canonical frame (ns = +z, ss = +x; the geometric normal ng, +z unless a test tilts it). sample == 0: out = {f.xyz, pdf}
-// for (wo, wi); sample == 1: out = {wi.xyz, f.xyz, pdf} for (wo, u).
+// for (wo, wi); sample == 1: out = {wi.xyz, f.xyz, pdf} for (wo, u); sample == 2: the same sample with the specular lobes allowed
+// (BSDF_ALL), out = {wi.xyz, f.xyz, pdf, sampled_specular, sampled_transmission}, the two flags as 0 or 1.
 __global__ void k_bsdf_probe(DScene S, int n, int mat, const float *wo, const float *wi_or_u, int sample, float *out, float ngx,
                              float ngy, float ngz) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -608,6 +609,20 @@ __global__ void k_bsdf_probe(DScene S, int n, int mat, const float *wo, const fl
         out[4 * i + 1] = f.y;
         out[4 * i + 2] = f.z;
         out[4 * i + 3] = bsdf_pdf(b, w, wi);
+    } else if (sample == 2) {
+        F3 wi = F3{0, 0, 0};
+        float pdf = 0;
+        bool spec = false, trans = false;
+        const F3 f = bsdf_sample_f(b, w, &wi, wi_or_u[2 * i], wi_or_u[2 * i + 1], &pdf, true, &spec, &trans);
+        out[9 * i] = wi.x;
+        out[9 * i + 1] = wi.y;
+        out[9 * i + 2] = wi.z;
+        out[9 * i + 3] = f.x;
+        out[9 * i + 4] = f.y;
+        out[9 * i + 5] = f.z;
+        out[9 * i + 6] = pdf;
+        out[9 * i + 7] = spec ? 1.f : 0.f;
+        out[9 * i + 8] = trans ? 1.f : 0.f;
     } else {
         F3 wi = F3{0, 0, 0};
         float pdf = 0;

@@ -306,6 +306,15 @@ class Oracle:
                                            out[i, 3:].ctypes.data, out[i, 6:].ctypes.data))
         return out
 
+    def bsdf_sample_specular(self, scene, mat, wo, u, trig_mode=TRIG_PORTABLE):
+        """{wi (3), f (3), pdf, sampled_specular, sampled_transmission} per (wo, u): Sample_f with the specular lobes allowed."""
+        wo, u = _f32(wo), _f32(u)
+        out = np.zeros((len(wo), 9), np.float32)
+        f = self.lib.oracle_bsdf_sample_specular
+        f.argtypes = [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]
+        _check("oracle_bsdf_sample_specular", f(scene.desc, trig_mode, mat, len(wo), wo.ctypes.data, u.ctypes.data, out.ctypes.data))
+        return out
+
     def bsdf_sample_batch(self, scene, mat, wo, u, trig_mode=TRIG_LIBM):
         wo, u = _f32(wo), _f32(u)
         n = len(u)

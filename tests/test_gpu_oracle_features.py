@@ -9,6 +9,7 @@ import pytest
 import boxroom
 from test_gpu_metal_substrate import CASES, PLANE, _direction_pairs, _sphere_dirs
 from test_gpu_parity import assert_bitwise
+from test_oracle_features import SPECULAR_CASES, specular_probe_inputs
 from quadric_ref import write_scene
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,26 @@ def test_bsdf_probes_bitwise(binding, oracle, tmp_path, case):
     assert_bitwise(dev[:, 3:], ref[:, 3:], f"{case}: bsdf_sample_ng f, pdf")
     ok = ref[:, 6] > 0
     assert_bitwise(dev[ok, :3], ref[ok, :3], f"{case}: bsdf_sample_ng wi")
+    gpu.close()
+
+
+@pytest.mark.parametrize("case", list(SPECULAR_CASES))
+def test_bsdf_probe_with_specular_lobes_bitwise(binding, oracle, tmp_path, case):
+    """bsdf_sample_f with allow_specular, as the path's bounce calls it: the pass-through, specular reflection, specular
+    transmission and FresnelSpecular lobes, which bsdf_sample never reaches. f, pdf and the two flags everywhere, wi where a
+    direction was sampled; plastic, which has no specular lobe, gives what bsdf_sample gives."""
+    host = binding.HostScene(path=write_scene(tmp_path, SPECULAR_CASES[case][0] + "\n" + PLANE + LIGHT, depth=1))
+    gpu = binding.GpuScene(host)
+    wo, u = specular_probe_inputs(case)
+    dev, ref = gpu.bsdf_sample_specular(0, wo, u), oracle.bsdf_sample_specular(host, 0, wo, u)
+    assert_bitwise(dev[:, 3:], ref[:, 3:], f"{case}: bsdf_sample_specular f, pdf, flags")
+    ok = ref[:, 6] > 0
+    assert ok.mean() > 0.5
+    assert_bitwise(dev[ok, :3], ref[ok, :3], f"{case}: bsdf_sample_specular wi")
+    if case == "plastic":
+        plain = gpu.bsdf_sample(0, wo, u)
+        assert_bitwise(dev[:, 3:7], plain[:, 3:], "plastic: bsdf_sample_specular against bsdf_sample")
+        assert_bitwise(dev[ok, :3], plain[ok, :3], "plastic: wi against bsdf_sample")
     gpu.close()
 
 

@@ -5,7 +5,10 @@
    wrong arrays. This list shrinks as features are restated.
 2. Metal and substrate, restated in oracle_path.cpp from metal.cpp, substrate.cpp and reflection.cpp, pinned to the float64
    restatement of microfacet_ref.py: f, pdf, sampled directions, a tilted geometric normal, and the alpha-0 metal.
-Both run in libm trig mode, the reference's own behaviour."""
+Both run in libm trig mode, the reference's own behaviour.
+3. Sample_f with the specular lobes allowed (oracle_bsdf_sample_specular): which lobe each u0 takes, the two flags, the exits
+   with pdf 0, and plastic against the existing mode. It runs in portable trig mode, the mode test_gpu_oracle_features.py holds
+   the device to it in, over the same inputs."""
 import numpy as np
 import pytest
 
@@ -180,3 +183,96 @@ def test_metal_alpha_zero(binding, oracle, tmp_path):
     fin = np.isfinite(f) & np.isfinite(out[:, :3])
     assert np.array_equal(np.isnan(out[:, :3]), np.isnan(f))
     assert np.allclose(out[:, :3][fin], f[fin], rtol=5e-5, atol=0)
+
+
+# ---- Sample_f with the specular lobes allowed ---------------------------------------------------------------------------------------
+# (material line, the lobes of its BSDF in BxDF order). R: specular reflection, T: specular transmission, F: FresnelSpecular
+# (reflection or transmission by the Fresnel term), g: a lobe that is not specular
+SPECULAR_CASES = {
+    "mirror": ('Material "mirror" "rgb Kr" [.9 .8 .7]', "R"),
+    "glass": ('Material "glass" "rgb Kr" [.9 .8 .7] "rgb Kt" [.6 .7 .8] "float index" [1.5]', "F"),
+    "glass_r_black": ('Material "glass" "rgb Kr" [0 0 0] "rgb Kt" [.6 .7 .8] "float index" [1.5]', "F"),
+    "uber_kr_only": ('Material "uber" "rgb Kd" [0 0 0] "rgb Ks" [0 0 0] "rgb Kr" [.8 .7 .6]', "R"),
+    "uber_five_lobes": ('Material "uber" "rgb Kd" [.3 .4 .5] "rgb Ks" [.4 .3 .2] "rgb Kr" [.5 .6 .7] "rgb Kt" [.7 .6 .5] '
+                        '"rgb opacity" [.4 .4 .4] "float index" [1.4]', "TggRT"),
+    "plastic": ('Material "plastic"', "gg"),
+}
+N_SPECULAR = 4000
+U0_TOP = np.float32(float.fromhex("0x1.fffffep-1"))
+
+
+def lobe_boundaries():
+    """every k / matching that u0 can meet with one to five lobes, the float just below each, and the largest float below 1"""
+    ks = sorted({float(np.float32(k) / np.float32(m)) for m in range(1, 6) for k in range(m)})
+    below = [float(np.nextafter(np.float32(v), np.float32(0))) for v in ks if v > 0]
+    return np.array(sorted(set(ks + below + [float(U0_TOP)])), np.float32)
+
+
+def specular_probe_inputs(case):
+    """(wo, u) of one case: wo on both sides of the surface, a fifth of them grazing (|wo.z| < 0.02: total internal reflection, and
+    wo.z == 0 itself, Sample_f's first exit); u0 from lobe_boundaries() for the first half — one boundary per five consecutive
+    directions, one of them grazing, the list tiled over the half, so every boundary meets grazing and other directions whatever
+    the seed —, uniform for the rest."""
+    rng = np.random.default_rng(4100 + sorted(SPECULAR_CASES).index(case))
+    n = N_SPECULAR
+    wo = _sphere_dirs(rng, n)
+    grazing = np.arange(n) % 5 == 0
+    phi = rng.random(n) * 2 * np.pi
+    z = rng.uniform(-0.02, 0.02, n)
+    z[:50] = 0
+    flat = np.stack([np.sqrt(1 - z * z) * np.cos(phi), np.sqrt(1 - z * z) * np.sin(phi), z], 1)
+    wo = np.where(grazing[:, None], flat, wo).astype(np.float32)
+    u = rng.random((n, 2)).astype(np.float32)
+    b = lobe_boundaries()
+    u[:n // 2, 0] = b[(np.arange(n // 2) // 5) % len(b)]
+    assert np.abs(wo[grazing, 2]).max() < 0.02 and (wo[:, 2] > 0.02).sum() > n // 4 and (wo[:, 2] < -0.02).sum() > n // 4
+    assert set(b.tolist()) <= set(u[grazing, 0].tolist()) and set(b.tolist()) <= set(u[~grazing, 0].tolist())
+    return wo, u
+
+
+@pytest.mark.parametrize("case", list(SPECULAR_CASES))
+def test_bsdf_sample_specular_lobes_and_flags(binding, oracle, tmp_path, case):
+    """The oracle's Sample_f with BSDF_ALL. Bit for bit: the lobe u0 picks (comp = min(floor(u0 n), n - 1), in float as the
+    reference multiplies) decides the two flags; a specular reflection is wo mirrored, with pdf 1 (mirror, uber) or the Fresnel
+    term (glass); plastic, without a specular lobe, gives what the existing mode gives; wo.z == 0 leaves everything zero; and where
+    pdf is 0 (total internal reflection in uber's Kt lobe) f and both flags are 0."""
+    line, lobes = SPECULAR_CASES[case]
+    host = binding.HostScene(path=write_scene(tmp_path, line + "\n" + PLANE + LIGHT, depth=1))
+    wo, u = specular_probe_inputs(case)
+    out = oracle.bsdf_sample_specular(host, 0, wo, u, trig_mode=ob.TRIG_PORTABLE)
+    wi, f, pdf, spec, trans = out[:, :3], out[:, 3:6], out[:, 6], out[:, 7], out[:, 8]
+    assert set(np.unique(out[:, 7:]).tolist()) <= {0.0, 1.0}
+    zero = wo[:, 2] == 0
+    assert zero.sum() == 10 and not out[zero].any()
+    dead = pdf == 0
+    assert not f[dead].any() and not spec[dead].any() and not trans[dead].any()
+    n = len(lobes)
+    comp = np.minimum(np.floor(u[:, 0] * np.float32(n)).astype(int), n - 1)
+    picked = np.array(list(lobes))[comp]
+    live = ~dead
+    assert (spec[live] == (picked[live] != "g")).all()
+    assert (trans[live & (picked == "T")] == 1).all() and (trans[live & (picked == "R")] == 0).all()
+    assert (trans[live & (picked == "g")] == 0).all()
+    refl = live & (spec == 1) & (trans == 0)
+    assert np.array_equal(wi[refl].view(np.uint32), (wo[refl] * np.float32([-1, -1, 1])).view(np.uint32))
+    thru = live & (trans == 1)
+    assert (wi[thru, 2] * wo[thru, 2] < 0).all()
+    if lobes == "F":
+        assert refl.any() and thru.any()   # both halves (under total internal reflection the Fresnel term is 1: it reflects)
+        assert not dead[~zero].any()
+        assert ((pdf[live] > 0) & (pdf[live] <= 1)).all()
+        if case == "glass_r_black":
+            assert not f[refl].any() and f[thru].all(axis=1).all()
+    elif lobes == "R":
+        assert refl.sum() == live.sum() == (~zero).sum() and (pdf[live] == 1).all()
+    elif case == "uber_five_lobes":
+        for k in range(n):   # every lobe taken, on both sides of the surface
+            assert (live & (comp == k) & (wo[:, 2] > 0)).any() and (live & (comp == k) & (wo[:, 2] < 0)).any(), k
+        assert (pdf[live & (picked != "g")] == np.float32(1) / np.float32(5)).all()
+        tir = dead & ~zero & (comp == 4)
+        assert tir.any() and (wo[tir, 2] < 0).all()   # total internal reflection: the Kt lobe, from inside only
+    else:
+        plain = oracle.bsdf_sample(host, 0, wo, u, trig_mode=ob.TRIG_PORTABLE)
+        assert np.array_equal(out[:, 3:7].view(np.uint32), plain[:, 3:].view(np.uint32)) and not out[:, 7:].any()
+        ok = plain[:, 6] > 0
+        assert np.array_equal(wi[ok].view(np.uint32), plain[ok, :3].view(np.uint32))
