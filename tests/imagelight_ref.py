@@ -1,95 +1,17 @@
 """The projection and goniometric lights of pbrt-v3 (src/lights/projection.cpp, src/lights/goniometric.{h,cpp}) restated in
-float64 numpy, vectorised over points, with the MIPMap they look their image up in (src/core/mipmap.h: the Lanczos resampling
-to powers of two, the box-filtered pyramid, the bilinear `triangle` with repeat wrap, `Lookup(st, width)`).
+float64 numpy, vectorised over points; the MIPMap they look their image up in (src/core/mipmap.h: the Lanczos resampling
+to powers of two, the box-filtered pyramid, the bilinear `triangle` with repeat wrap, `Lookup(st, width)`) is mipmap_ref.py's.
 
 The CPU oracle has neither light and the reference cannot be built here, so this is the independent statement the loader and
 the device are held to (test_image_light_scenes.py, test_gpu_image_lights.py). An image is an (h, w, 3) array as ReadImage
 returns it: row 0 is the TOP scanline, and neither light flips it."""
 import numpy as np
 
+# the MIPMap of src/core/mipmap.h and its resampling helpers live in mipmap_ref.py, with all three wrap modes and EWA
+from mipmap_ref import MipMap, _round_up_pow2  # noqa: F401  (_round_up_pow2: test_image_light_scenes.py sizes level 0 with it)
+
 HITHER = float(np.float32(1e-3))
 YON = float(np.float32(1e30))
-
-
-# ---- MIPMap -----------------------------------------------------------------------------------------------------------------
-def _round_up_pow2(v):
-    return 1 << (int(v) - 1).bit_length()
-
-
-def _lanczos(x, tau=2.0):
-    """Lanczos(x, tau), src/core/texture.cpp:51-58."""
-    x = np.abs(x)
-    xs = np.where(x < 1e-5, 1.0, x) * np.pi
-    val = np.sin(xs * tau) / (xs * tau) * (np.sin(xs) / xs)
-    return np.where(x < 1e-5, 1.0, np.where(x > 1.0, 0.0, val))
-
-
-def _resample_weights(old, new):
-    """MIPMap::resampleWeights (mipmap.h:206-225): (first texel, four normalised weights) per new texel."""
-    center = (np.arange(new) + 0.5) * old / new
-    first = np.floor(center - 2.0 + 0.5).astype(int)
-    pos = first[:, None] + np.arange(4)[None, :] + 0.5
-    w = _lanczos((pos - center[:, None]) / 2.0)
-    return first, w / w.sum(1, keepdims=True)
-
-
-def resample_pow2(img):
-    """The constructor's resampling of an image whose sides are not powers of two (mipmap.h:126-180), repeat wrap: s, then t,
-    then a clamp to [0, inf)."""
-    img = np.asarray(img, np.float64)
-    h, w, _ = img.shape
-    wp, hp = _round_up_pow2(w), _round_up_pow2(h)
-    if (wp, hp) == (w, h):
-        return img
-    first, wt = _resample_weights(w, wp)
-    cols = (first[:, None] + np.arange(4)[None, :]) % w
-    tmp = (img[:, cols, :] * wt[None, :, :, None]).sum(2)  # (h, wp, 3)
-    first, wt = _resample_weights(h, hp)
-    rows = (first[:, None] + np.arange(4)[None, :]) % h
-    out = (tmp[rows, :, :] * wt[:, :, None, None]).sum(1)  # (hp, wp, 3)
-    return np.maximum(out, 0.0)
-
-
-class MipMap:
-    """MIPMap<RGBSpectrum>(resolution, texels) with its defaults (repeat wrap)."""
-
-    def __init__(self, img):
-        level = resample_pow2(img)
-        self.levels = [level]
-        while max(level.shape[:2]) > 1:  # mipmap.h:183-197
-            h, w, _ = level.shape
-            nh, nw = max(1, h // 2), max(1, w // 2)
-            t, s = np.arange(nh)[:, None], np.arange(nw)[None, :]
-            tx = lambda ss, tt: level[tt % h, ss % w]
-            level = 0.25 * (tx(2 * s, 2 * t) + tx(2 * s + 1, 2 * t) + tx(2 * s, 2 * t + 1) + tx(2 * s + 1, 2 * t + 1))
-            self.levels.append(level)
-
-    def texel(self, level, s, t):
-        a = self.levels[level]
-        return a[t % a.shape[0], s % a.shape[1]]
-
-    def triangle(self, level, st):
-        """MIPMap::triangle (mipmap.h:252-262)."""
-        level = min(max(level, 0), len(self.levels) - 1)
-        h, w, _ = self.levels[level].shape
-        s, t = st[..., 0] * w - 0.5, st[..., 1] * h - 0.5
-        s0, t0 = np.floor(s).astype(int), np.floor(t).astype(int)
-        ds, dt = (s - s0)[..., None], (t - t0)[..., None]
-        return ((1 - ds) * (1 - dt) * self.texel(level, s0, t0) + (1 - ds) * dt * self.texel(level, s0, t0 + 1) +
-                ds * (1 - dt) * self.texel(level, s0 + 1, t0) + ds * dt * self.texel(level, s0 + 1, t0 + 1))
-
-    def lookup(self, st, width=0.0):
-        """MIPMap::Lookup(st, width) (mipmap.h:233-250)."""
-        st = np.asarray(st, np.float64)
-        n = len(self.levels)
-        level = n - 1 + np.log2(max(width, 1e-8))
-        if level < 0:
-            return self.triangle(0, st)
-        if level >= n - 1:
-            return np.broadcast_to(self.texel(n - 1, 0, 0), st.shape[:-1] + (3,)).copy()
-        il = int(np.floor(level))
-        delta = level - il
-        return (1 - delta) * self.triangle(il, st) + delta * self.triangle(il + 1, st)
 
 
 # ---- the lights -------------------------------------------------------------------------------------------------------------
