@@ -351,6 +351,11 @@ void iile_traversal_limits(int32_t *out3);
 /* Light::Sample_Li of delta light `light` (point, spot, distant, projection, goniometric: iile_light_is_delta; any other is
  * IILE_ERR_ARG) at n points p3, each an Interaction without a surface: out7 = {wi.xyz, Li.rgb, pdf} per point. */
 int iile_light_sample_li(iile_scene *scene, int32_t light, int32_t n, const float *p3, float *out7);
+/* The light the path integrator's UniformSampleOneLight samples at each of n points p3 with the 1D sample u[i], and the pdf of
+ * that choice, under the scene's "lightsamplestrategy" (LightDistribution::Lookup + Distribution1D::SampleDiscrete,
+ * integrator.cpp:85-106). A scene of one light: light 0 with pdf 1. Queued on `stream` (NULL: the null stream), which is drained
+ * before it returns. */
+int iile_light_choose(iile_scene *scene, int32_t n, const float *p3, const float *u, int32_t *out_light, float *out_pdf, void *stream);
 /* ImageTexture<RGBSpectrum, Spectrum>::Evaluate (src/textures/imagemap.h:87-94) of image texture `tex` at n
  * surface points given by (u, v) and the screen-space differentials {du/dx, dv/dx, du/dy, dv/dy}. */
 int iile_texture_eval(iile_scene *scene, int32_t tex, int32_t n, const float *uv2, const float *duv4, float *rgb3);

@@ -183,7 +183,9 @@ enum { IILE_AA_CLOSEDFORM = 0, IILE_AA_NONE = 1 };
  * PointLight (src/lights/point.h:49-70), SpotLight (src/lights/spot.h:49-74), DistantLight
  * (src/lights/distant.h:49-72), ProjectionLight (src/lights/projection.h:49-76), GonioPhotometricLight
  * (src/lights/goniometric.h:52-91). */
-#define IILE_MAX_LIGHTS 8 /* the device keeps per-voxel light distributions for this many */
+/* Not a limit on the scene's lights (iile_scene_desc::n_lights is any number; every emitting triangle is a light of its own): the
+ * length of iile_integrator::light_power, which holds the first eight lights' power. iile_scene_desc::light_power_all holds all. */
+#define IILE_MAX_LIGHTS 8
 #define IILE_LIGHT_DIFFUSE_AREA 0
 #define IILE_LIGHT_POINT 1
 #define IILE_LIGHT_SPOT 2
@@ -315,7 +317,7 @@ typedef struct iile_integrator {
     int32_t max_depth;
     float rr_threshold;
     int32_t light_strategy;             /* "lightsamplestrategy" of the path integrator (path.cpp:231), IILE_LIGHTS_* */
-    float light_power[IILE_MAX_LIGHTS]; /* power strategy: Power().y() of every light */
+    float light_power[IILE_MAX_LIGHTS]; /* power strategy: Power().y() of the first IILE_MAX_LIGHTS lights (all of them: iile_scene_desc::light_power_all) */
     /* "pixelbounds" (path.cpp:216-229): {x0, y0, x1, y1} = Intersect(film->GetSampleBounds(), the four values given); pixels of the
      * sample bounds outside it take no samples (SamplerIntegrator::Render, integrator.cpp:272). The sample bounds when not given;
      * all four zero = not given (what a caller that does not know the field leaves); the host writes an empty intersection as {0, 0, -1, -1} */
@@ -377,6 +379,9 @@ typedef struct iile_scene_desc {
     /* disks and cylinders (appended last: the layout before them is what it was without them) */
     int32_t n_quadrics;
     const iile_quadric *quadrics;
+    /* every light's power (appended last, as the quadrics were: a descriptor of the size before it is still read correctly while
+     * it holds at most IILE_MAX_LIGHTS lights) */
+    const float *light_power_all; /* [n_lights]: Power().y() of every light; read only when n_lights > IILE_MAX_LIGHTS */
 } iile_scene_desc;
 
 /* One task of the IISPT render runner (IisptScheduleMonitorTask, src/integrators/iisptschedulemonitor.cpp:40-79): the

@@ -122,6 +122,42 @@ class SceneDescHead(ctypes.Structure):
                 ("prim_light", c_vp), ("prim_shape", c_vp), ("tri_p", c_vp)]
 
 
+class _Halton(ctypes.Structure):
+    _fields_ = [("spp", c_i32), ("base_scales", c_i32 * 2), ("base_exponents", c_i32 * 2), ("sample_stride", c_i32),
+                ("mult_inverse", c_i32 * 2), ("n_dims", c_i32), ("perms", c_vp), ("primes", c_vp), ("prime_sums", c_vp),
+                ("n_perms", c_i32), ("sample_at_pixel_center", c_i32)]
+
+
+class Integrator(ctypes.Structure):
+    """iile_integrator (include/iile_scene.h); light_power holds the first MAX_LIGHTS lights' power."""
+    _fields_ = [("max_depth", c_i32), ("rr_threshold", c_f32), ("light_strategy", c_i32), ("light_power", c_f32 * 8),
+                ("pixel_bounds", c_i32 * 4)]
+
+
+class _ProbeSetup(ctypes.Structure):
+    _fields_ = [("hemi_size", c_i32), ("max_depth", c_i32), ("film", FilmDesc), ("filter_table", c_f32 * 256), ("base_scales", c_i32 * 2),
+                ("base_exponents", c_i32 * 2), ("sample_stride", c_i32), ("mult_inverse", c_i32 * 2)]
+
+
+class _Sobol(ctypes.Structure):
+    _fields_ = [("enabled", c_i32), ("spp", c_i32), ("resolution", c_i32), ("log2_resolution", c_i32), ("n_dims", c_i32),
+                ("matrices32", c_vp), ("vdc", c_u32 * 32), ("vdc_inv", c_u32 * 32)]
+
+
+class SceneDesc(ctypes.Structure):
+    """The whole iile_scene_desc (include/iile_scene.h), light_power_all at its end."""
+    _fields_ = SceneDescHead._fields_ + [
+        ("tri_n", c_vp), ("tri_uv", c_vp), ("prim_alpha", c_vp), ("n_spheres", c_i32), ("spheres", c_vp), ("n_materials", c_i32),
+        ("materials", c_vp), ("n_lights", c_i32), ("lights", c_vp), ("n_env_dist", ctypes.c_int64), ("env_dist", c_vp),
+        ("n_textures", c_i32), ("textures", c_vp), ("n_texels", ctypes.c_int64), ("texels", c_vp), ("ewa_lut", c_f32 * 128),
+        ("film_filter_wide", c_i32), ("film_filter_table", c_f32 * 256), ("camera", Camera), ("film", FilmDesc), ("halton", _Halton),
+        ("integrator", Integrator), ("probe", _ProbeSetup), ("sobol", _Sobol), ("n_quadrics", c_i32), ("quadrics", c_vp),
+        ("light_power_all", c_vp)]
+
+
+MAX_LIGHTS = 8  # IILE_MAX_LIGHTS: the length of iile_integrator::light_power, not a limit on the lights of a scene
+
+
 class Quadric(ctypes.Structure):
     """iile_quadric (include/iile_scene.h): a disk or a cylinder."""
     _fields_ = [("o2w", c_f32 * 16), ("o2w_inv", c_f32 * 16), ("kind", c_i32), ("radius", c_f32), ("inner_radius", c_f32),
@@ -190,7 +226,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
-               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_bsdf_sample_specular", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_render_probes",
+               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_bsdf_sample_specular", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_light_choose", "iile_render_probes",
                "iile_render_probes_reference", "iile_test_probe_ref_group", "iile_reference_points",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
@@ -309,6 +345,7 @@ def gpu_lib():
         lib.iile_bsdf_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_texture_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_light_sample_li.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp]
+        lib.iile_light_choose.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         lib.iile_texture_eval_p.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_render_probes.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, ctypes.POINTER(GpuStats), c_vp]
         lib.iile_render_probes_reference.argtypes = [c_vp, c_i32, c_vp, c_vp, ctypes.POINTER(ProbeRefParams), c_vp, c_vp, c_vp, c_vp,
@@ -523,6 +560,27 @@ class HostScene:
             raise RuntimeError(host_lib().iile_host_last_error().decode())
         return lt
 
+    def scene_desc(self):
+        """The scene's iile_scene_desc as a SceneDesc (a copy of the struct; its pointers are the scene's own tables)."""
+        return SceneDesc.from_buffer_copy(ctypes.string_at(self.desc, ctypes.sizeof(SceneDesc)))
+
+    @property
+    def light_count(self):
+        return int(self.scene_desc().n_lights)
+
+    def light_power_all(self):
+        """iile_scene_desc::light_power_all: Power().y() of every light (a copy); its first MAX_LIGHTS entries are also
+        iile_integrator::light_power."""
+        d = self.scene_desc()
+        if not d.light_power_all:
+            raise RuntimeError("the scene's descriptor has no light_power_all")
+        return np.frombuffer(ctypes.string_at(d.light_power_all, d.n_lights * 4), dtype=np.float32).copy()
+
+    def prim_light(self):
+        """iile_scene_desc::prim_light, in BVH order (a copy): the light a primitive is, or -1."""
+        head = ctypes.cast(self.desc, ctypes.POINTER(SceneDescHead)).contents
+        return np.frombuffer(ctypes.string_at(head.prim_light, head.n_prims * 4), dtype=np.int32).copy()
+
     def camera(self):
         """(CAMERA_PERSPECTIVE or CAMERA_ENVIRONMENT, the scene's iile_camera as a copy)."""
         cam = Camera()
@@ -722,6 +780,15 @@ class GpuScene:
         out = np.empty((len(p), 7), np.float32)
         self._check(gpu_lib().iile_light_sample_li(self._s, int(light), len(p), p.ctypes.data, out.ctypes.data), "iile_light_sample_li")
         return out
+
+    def light_choose(self, p, u, stream=None):
+        """The light UniformSampleOneLight samples at the (n, 3) points p with the 1D samples u, under the scene's light strategy:
+        (light (n,) int32, pdf (n,) float32). One light: light 0 with pdf 1."""
+        p, u = _f32(p).reshape(-1, 3), _f32(u).reshape(-1)
+        light, pdf = np.empty(len(u), np.int32), np.empty(len(u), np.float32)
+        self._check(gpu_lib().iile_light_choose(self._s, len(u), p.ctypes.data, u.ctypes.data, light.ctypes.data, pdf.ctypes.data,
+                                                c_vp(stream) if stream else None), "iile_light_choose")
+        return light, pdf
 
     def render_probes(self, pos, direction, hemi=None, device_out=None, stream=None):
         """IISPT probe pass: (n, 3) origins and directions -> intensity (n, hemi, hemi, 3), camera-space normals

@@ -110,7 +110,7 @@ struct iile_scene {
     int n_cus = 256;
     int max_depth = 5;
     int spp = 1;
-    int light_samples[8] = {1, 1, 1, 1, 1, 1, 1, 1};  // Light::nSamples (iile_light::n_samples), the direct pass's nLightSamples
+    std::vector<int> light_samples;                   // Light::nSamples of every light (iile_light::n_samples, at least 1), the direct pass's nLightSamples
     std::vector<int> light_types;                     // iile_light::type of every light (iile_light_sample_li checks it)
     // wavefront workspace, grown on demand and kept across renders (ensure_workspace carves pb from it)
     uint32_t ws_paths = 0;

@@ -40,7 +40,7 @@ int iile_render_direct(iile_scene *sc, const iile_direct_params *prm, double *fi
     // pass keeps its own seed and its own records; the fold adds a pixel's passes in pass order. Glass (one thread per pixel
     // walking a tree) stays at one pass per launch.
     int total_samples_pre = 0;
-    for (int l = 0; l < std::max(S.n_lights, 0) && l < 8; ++l) total_samples_pre += std::max(1, sc->light_samples[l]);
+    for (int l = 0; l < std::max(S.n_lights, 0); ++l) total_samples_pre += sc->light_samples[size_t(l)];
     const uint64_t pixels64 = uint64_t(P.n_owned_tiles) * 256;
     int batch = (S.has_glass != 0) ? 1 : std::max(1, std::min(prm->n_passes, 4));
     while (batch > 1 && pixels64 * uint64_t(batch) * uint64_t(std::max(total_samples_pre, 1)) > 100000000ull) --batch;   // NEE records per level (8 passes at a time measured no faster than 4)
@@ -56,11 +56,8 @@ int iile_render_direct(iile_scene *sc, const iile_direct_params *prm, double *fi
     // paths alone overflowed from 4 lights on at 1080p; found by the round-3 advisor)
     // UniformSampleAllLights takes Light::nSamples samples of every light (directprogressiveintegrator.cpp:9-18, integrator.cpp:54-83)
     const int n_lights = std::max(S.n_lights, 0), n_arrays = 5 * n_lights * 2;
-    int total_samples = 0;
-    for (int l = 0; l < n_lights && l < 8; ++l) {
-        P.direct_nsamples[l] = std::max(1, sc->light_samples[l]);
-        total_samples += P.direct_nsamples[l];
-    }
+    const std::vector<int> &nsamples = sc->light_samples;
+    const int total_samples = total_samples_pre;
     P.direct_total_samples = total_samples;
     if (total_samples > 64)
         return api_fail(IILE_ERR_UNSUPPORTED, "iile_render_direct: " + std::to_string(total_samples) + " light samples per vertex (the lights' nsamples summed; at most 64)");
@@ -81,11 +78,13 @@ int iile_render_direct(iile_scene *sc, const iile_direct_params *prm, double *fi
     const bool with_rd = reflect_diffs && !tree;
     float4 *D = nullptr, *RD = nullptr;
     unsigned long long *jump_dev = nullptr;
+    int *nsamples_dev = nullptr;
     double *film_dev = film_rgbw;
     auto layout = [&](Carver c) {
         D = c.take<float4>(d_recs + 2 * ef_recs);   // D, E, F: one range, cleared by one memset per launch
         if (with_rd) RD = c.take<float4>(4 * np);
         jump_dev = c.take<unsigned long long>((size_t(n_arrays) + 1) * 2);
+        nsamples_dev = c.take<int>(size_t(n_lights));
         if (!prm->film_on_device) film_dev = c.take<double>(size_t(fw) * fh * 4);
         return c.used;
     };
@@ -102,13 +101,14 @@ int iile_render_direct(iile_scene *sc, const iile_direct_params *prm, double *fi
         for (int i = 0; i <= n_arrays; ++i) {
             jump[2 * size_t(i)] = A;
             jump[2 * size_t(i) + 1] = G;
-            const int draws = i < n_arrays ? 32 * P.direct_nsamples[(i / 2) % std::max(n_lights, 1)] : 0;
+            const int draws = i < n_arrays ? 32 * nsamples[size_t((i / 2) % std::max(n_lights, 1))] : 0;
             for (int s = 0; s < draws; ++s) {  // one more draw: state' = a state + inc
                 G = G * a + 1;
                 A = A * a;
             }
         }
         HIP_TRY(hipMemcpyAsync(jump_dev, jump.data(), jump_bytes, hipMemcpyHostToDevice, stream));
+        if (n_lights > 0) HIP_TRY(hipMemcpyAsync(nsamples_dev, nsamples.data(), size_t(n_lights) * sizeof(int), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));  // (the vector dies with this scope)
     }
     if (!prm->accumulate) HIP_TRY(hipMemsetAsync(film_dev, 0, film_bytes, stream));
@@ -122,6 +122,7 @@ int iile_render_direct(iile_scene *sc, const iile_direct_params *prm, double *fi
     B.spill = sc->spill;
     P.direct_arrays = n_arrays;
     P.direct_jump = jump_dev;
+    P.direct_nsamples = nsamples_dev;
     for (int i = 0; i < prm->n_passes; i += batch) {
         const int nb = std::min(batch, prm->n_passes - i);   // (the last launch may hold fewer passes: same buffers, fewer paths)
         P.kc = nb;

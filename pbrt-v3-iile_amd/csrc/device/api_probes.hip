@@ -1,5 +1,5 @@
 // api_probes.hip — the kernel-level entry points of the C ABI (include/iile_gpu.h): single kernels and device functions
-// run on arrays of the caller's, for the parity tests. All of them work on the null stream and return with the device
+// run on arrays of the caller's, for the parity tests. All of them work on the null stream (iile_light_choose: on the caller's) and return with the device
 // drained.
 #include <cstring>
 
@@ -154,6 +154,28 @@ int iile_light_sample_li(iile_scene *sc, int32_t light, int32_t n, const float *
     if ((rc = dp.put(p3, 3 * size_t(n))) || (rc = dout.alloc(7 * size_t(n)))) return rc;
     if (n) launch_light_probe(sc->ds, n, light, dp.p, dout.p, probe_cfg(sc));
     return finish(dout, out7, 7 * size_t(n));
+}
+
+int iile_light_choose(iile_scene *sc, int32_t n, const float *p3, const float *u, int32_t *out_light, float *out_pdf, void *stream) {
+    if (!sc || n < 0 || !p3 || !u || !out_light || !out_pdf) return api_fail(IILE_ERR_ARG, "iile_light_choose: bad argument");
+    if (sc->ds.n_lights < 1) return api_fail(IILE_ERR_ARG, "iile_light_choose: the scene has no light");
+    int rc = ensure_device();
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DevBuf<float> dp, du, dpdf;
+    DevBuf<int> dl;
+    if ((rc = dp.alloc(3 * size_t(n))) || (rc = du.alloc(size_t(n))) || (rc = dl.alloc(size_t(n))) || (rc = dpdf.alloc(size_t(n)))) return rc;
+    if (n == 0) return IILE_OK;
+    HIP_TRY(hipMemcpyAsync(dp.p, p3, 3 * size_t(n) * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(du.p, u, size_t(n) * sizeof(float), hipMemcpyHostToDevice, s));
+    LaunchCfg cfg = probe_cfg(sc);
+    cfg.stream = s;
+    launch_light_choose(sc->ds, n, dp.p, du.p, dl.p, dpdf.p, cfg);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_light, dl.p, size_t(n) * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_pdf, dpdf.p, size_t(n) * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IILE_OK;
 }
 
 int iile_texture_eval(iile_scene *sc, int32_t tex, int32_t n, const float *uv2, const float *duv4, float *rgb3) {

@@ -95,6 +95,20 @@ bool prim_masked(const iile_scene_desc &d, int i) {
     return (d.prim_flags[i] & IILE_PRIM_HAS_ALPHA) && d.prim_alpha &&
            (d.prim_alpha[2 * i] != IILE_ALPHA_NONE || d.prim_alpha[2 * i + 1] != IILE_ALPHA_NONE);
 }
+// SpatialLightDistribution's voxel grid over the scene bounds (lightdistrib.cpp:98-111): up to 64 voxels per axis, cubes along the
+// longest one. The bounds are the root node's.
+void light_grid(const iile_scene_desc &d, int nv[3]) {
+    const float *lo = d.nodes[0].bmin, *hi = d.nodes[0].bmax;
+    const float diag[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    const int me = (diag[0] > diag[1] && diag[0] > diag[2]) ? 0 : (diag[1] > diag[2] ? 1 : 2);  // MaximumExtent
+    const float bmax = diag[me];
+    for (int i = 0; i < 3; ++i) nv[i] = std::max(1, int(std::round(diag[i] / bmax * 64)));
+}
+// The dense table of the spatial strategy, one record of 2 n + 2 floats per voxel, may take this much device memory: 511 lights on
+// a full 64^3 grid. A design decision, not a measurement; the reference fills its voxels lazily and has no such limit.
+constexpr uint64_t kMaxLightTableBytes = uint64_t(1) << 30;
+bool spatial_table(const iile_scene_desc &d) { return d.n_lights > 1 && d.integrator.light_strategy == IILE_LIGHTS_SPATIAL && d.n_nodes > 0; }
+
 int interior_nodes(const iile_scene_desc &d) {
     return int(std::count_if(d.nodes, d.nodes + std::max(d.n_nodes, 0), [](const iile_bvh_node &nd) { return nd.nprims == 0; }));
 }
@@ -118,8 +132,12 @@ int bvh_depth(const iile_bvh_node *nodes, int n_nodes) {
 int check_scene_desc(const iile_scene_desc &d) {
     // what the device path supports
     if (d.n_prims >= (1 << 24)) return api_fail(IILE_ERR_UNSUPPORTED, "more than 2^24 primitives");
-    if (d.n_spheres > kMaxSpheres || d.n_materials > kMaxMaterials || d.n_lights > kMaxLights)
-        return api_fail(IILE_ERR_UNSUPPORTED, "too many spheres / materials / lights");
+    if (d.n_spheres > kMaxSpheres || d.n_materials > kMaxMaterials) return api_fail(IILE_ERR_UNSUPPORTED, "too many spheres / materials");
+    if (d.n_lights < 0 || (d.n_lights > 0 && !d.lights)) return api_fail(IILE_ERR_ARG, "n_lights without lights");
+    // (light_power_all lies behind the members an older caller's descriptor has: not touched unless the lights need it)
+    if (d.n_lights > IILE_MAX_LIGHTS && d.integrator.light_strategy == IILE_LIGHTS_POWER && !d.light_power_all)
+        return api_fail(IILE_ERR_ARG, "light_power_all is null: the power strategy over more than " + std::to_string(IILE_MAX_LIGHTS) +
+                                          " lights reads every light's power there");
     if (d.n_quadrics < 0 || d.n_quadrics > kMaxQuadrics || (d.n_quadrics > 0 && !d.quadrics))
         return api_fail(IILE_ERR_UNSUPPORTED, "too many disks and cylinders");
     for (int i = 0; i < d.n_quadrics; ++i)
@@ -163,6 +181,17 @@ int check_scene_desc(const iile_scene_desc &d) {
     // the references between the tables
     int n_interior = 0;
     if (const int rc = check_bvh_nodes(d.nodes, d.n_nodes, d.n_prims, "", &n_interior)) return rc;
+    if (spatial_table(d)) {
+        int nv[3];
+        light_grid(d, nv);
+        const uint64_t bytes = uint64_t(nv[0]) * uint64_t(nv[1]) * uint64_t(nv[2]) * (2 * uint64_t(d.n_lights) + 2) * sizeof(float);
+        if (bytes > kMaxLightTableBytes)
+            return api_fail(IILE_ERR_UNSUPPORTED,
+                            std::to_string(d.n_lights) + " lights: the spatial light distribution's table over " + std::to_string(nv[0]) + " x " +
+                                std::to_string(nv[1]) + " x " + std::to_string(nv[2]) + " voxels would take " + std::to_string(bytes >> 20) +
+                                " MiB (at most " + std::to_string(kMaxLightTableBytes >> 20) +
+                                "); \"lightsamplestrategy\" \"power\" or \"uniform\" renders the scene");
+    }
     // a lane's traversal stack holds a tree of traversal_limits().max_bvh_depth levels (dtrav.h: kMaxBvhDepth); a deeper one could
     // write past the lane's HBM column into its neighbours'
     const int depth = bvh_depth(d.nodes, d.n_nodes), max_depth = traversal_limits().max_bvh_depth;
@@ -392,13 +421,13 @@ int build_prims(iile_scene *sc, const iile_scene_desc &d) {
     for (size_t i = 0; i < n; ++i) {
         const float *p = d.tri_p + 9 * i, *nn = d.tri_n + 9 * i, *uv = d.tri_uv + 6 * i;
         // flag word: bits 0..3 iile_scene.h (bit 0 set for a sphere AND for a quadric: not a triangle, the shape is
-        // told by prim_shape), bit 4 last primitive of its leaf, bits 5..7 shading class, bits 8..11 area light index + 1,
-        // bit 12 alpha-masked
+        // told by prim_shape), bit 4 last primitive of its leaf, bits 5..7 shading class, bit 8 an area light (which one: the
+        // third word; bits 9..11 stay clear, hit_tag in dtrav.h carries bits 5..11 along), bit 12 alpha-masked
         const uint32_t f = d.prim_flags[i];
         const bool quadric = (f & IILE_PRIM_QUADRIC) != 0;
         const int mt = d.prim_material[i] >= 0 ? d.materials[d.prim_material[i]].type : 3;
         uint32_t w[3] = {(f & 15u) | (quadric ? 1u : 0u) | (prim_masked(d, int(i)) ? 4096u : 0u) | last_in_leaf[i] |
-                             shading_class(mt, (f & IILE_PRIM_SPHERE) || quadric) << 5 | (uint32_t(d.prim_light[i] + 1) << 8),
+                             shading_class(mt, (f & IILE_PRIM_SPHERE) || quadric) << 5 | (d.prim_light[i] >= 0 ? 256u : 0u),
                          uint32_t(d.prim_material[i]), uint32_t(d.prim_light[i])};
         for (int k = 0; k < 3; ++k) {
             float wf;
@@ -512,7 +541,8 @@ int build_textures(iile_scene *sc, const iile_scene_desc &d) {
 int build_lights(iile_scene *sc, const iile_scene_desc &d) {
     DScene &S = sc->ds;
     S.n_lights = d.n_lights;
-    for (int i = 0; i < d.n_lights && i < 8; ++i) sc->light_samples[i] = std::max(1, int(d.lights[i].n_samples));
+    sc->light_samples.resize(size_t(d.n_lights));
+    for (int i = 0; i < d.n_lights; ++i) sc->light_samples[size_t(i)] = std::max(1, int(d.lights[i].n_samples));
     for (int i = 0; i < d.n_lights; ++i) sc->light_types.push_back(d.lights[i].type);
     std::vector<DLight> lts(d.n_lights);
     for (int i = 0; i < d.n_lights; ++i) {
@@ -669,18 +699,21 @@ int build_runtime(iile_scene *sc, const iile_scene_desc &) {
     return IILE_OK;
 }
 
-// More than one light: tabulate the spatial light distribution (lightdistrib.cpp:91-299) for every voxel of its grid — up
-// to 64 per axis, cubes along the longest one.
+// More than one light: tabulate the spatial light distribution (lightdistrib.cpp:91-299) for every voxel of its grid
+// (light_grid). A Distribution1D over the n lights is a record func[n] | cdf[n + 1] | funcInt.
 int build_light_distribution(iile_scene *sc, const iile_scene_desc &d) {
     DScene &S = sc->ds;
     S.light_nv[0] = S.light_nv[1] = S.light_nv[2] = 1;
-    if (d.n_lights > 1 && d.integrator.light_strategy != IILE_LIGHTS_SPATIAL) {
+    const int n = d.n_lights;
+    const size_t stride = light_record_floats(n);
+    if (n > 1 && d.integrator.light_strategy != IILE_LIGHTS_SPATIAL) {
         // UniformLightDistribution / PowerLightDistribution (lightdistrib.cpp:65-82, integrator.cpp:217-225): one
         // Distribution1D for every point — a grid of a single voxel, built here (sampling.h:57-69)
-        std::vector<float> tab(size_t(kLightDistStride), 0.f);
-        const int n = d.n_lights;
-        float *func = tab.data(), *cdf = tab.data() + kMaxLights;
-        for (int i = 0; i < n; ++i) func[i] = d.integrator.light_strategy == IILE_LIGHTS_UNIFORM ? 1.f : d.integrator.light_power[i];
+        std::vector<float> tab(stride, 0.f);
+        // (the first IILE_MAX_LIGHTS powers have always been the integrator's; a descriptor with no more lights may end before light_power_all)
+        const float *power = n > IILE_MAX_LIGHTS ? d.light_power_all : d.integrator.light_power;
+        float *func = tab.data(), *cdf = tab.data() + n;
+        for (int i = 0; i < n; ++i) func[i] = d.integrator.light_strategy == IILE_LIGHTS_UNIFORM ? 1.f : power[i];
         cdf[0] = 0;
         for (int i = 1; i < n + 1; ++i) cdf[i] = cdf[i - 1] + func[i - 1] / n;
         const float func_int = cdf[n];
@@ -688,14 +721,11 @@ int build_light_distribution(iile_scene *sc, const iile_scene_desc &d) {
             for (int i = 1; i < n + 1; ++i) cdf[i] = float(i) / float(n);
         else
             for (int i = 1; i < n + 1; ++i) cdf[i] /= func_int;
-        tab[2 * kMaxLights + 1] = func_int;
+        tab[2 * size_t(n) + 1] = func_int;
         return upload(sc, tab.data(), tab.size(), &S.light_dist);
     }
-    if (d.n_lights <= 1 || d.n_nodes <= 0) return IILE_OK;
-    const float diag[3] = {S.root_box[3] - S.root_box[0], S.root_box[4] - S.root_box[1], S.root_box[5] - S.root_box[2]};
-    const int me = (diag[0] > diag[1] && diag[0] > diag[2]) ? 0 : (diag[1] > diag[2] ? 1 : 2);  // MaximumExtent
-    const float bmax = diag[me];
-    for (int i = 0; i < 3; ++i) S.light_nv[i] = std::max(1, int(std::round(diag[i] / bmax * 64)));
+    if (!spatial_table(d)) return IILE_OK;
+    light_grid(d, S.light_nv);
     // RadicalInverse(0..4, i), i < 128 (lowdiscrepancy.cpp:389-444): bases 2, 3, 5, 7, 11
     std::vector<float> samples(128 * 5);
     const int bases[5] = {2, 3, 5, 7, 11};
@@ -722,7 +752,7 @@ int build_light_distribution(iile_scene *sc, const iile_scene_desc &d) {
     float *dist = nullptr;
     const size_t n_vox = size_t(S.light_nv[0]) * S.light_nv[1] * S.light_nv[2];
     int rc = upload(sc, samples.data(), samples.size(), &dsamples);
-    if (!rc) rc = scene_alloc(sc, n_vox * kLightDistFloats * sizeof(float), &dist, "hipMalloc(light distributions) failed");
+    if (!rc) rc = scene_alloc(sc, n_vox * stride * sizeof(float), &dist, "hipMalloc(light distributions) failed");
     if (rc) return rc;
     S.light_dist = dist;
     LaunchCfg cfg{sc->n_cus, nullptr, false};

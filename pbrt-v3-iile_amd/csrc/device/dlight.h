@@ -363,3 +363,36 @@ DEV F3 delta_light_li(const DScene &S, const DLight &lt, F3 p, F3 *wi, F3 *targe
     }
     return sdiv(I * falloff, length_sq(pos - p));
 }
+// ===========================================================================
+// choosing a light: SpatialLightDistribution::Lookup (lightdistrib.cpp:134-226; the voxels are tabulated at scene creation,
+// kernels_shade.hip) + Distribution1D::SampleDiscrete (sampling.h:90-100, FindInterval pbrt.h:399-412). The uniform and power
+// strategies keep a grid of one voxel. A record is func[n] | cdf[n + 1] | funcInt; the whole table stays under 2^28 floats.
+// ===========================================================================
+DEV int sample_light(const DScene &S, F3 p, float u, float *pdf) {
+    const F3 bmin = F3{S.root_box[0], S.root_box[1], S.root_box[2]}, bmax = F3{S.root_box[3], S.root_box[4], S.root_box[5]};
+    F3 o = p - bmin;  // Bounds3::Offset, geometry.h:800-806
+    if (bmax.x > bmin.x) o.x = o.x / (bmax.x - bmin.x);
+    if (bmax.y > bmin.y) o.y = o.y / (bmax.y - bmin.y);
+    if (bmax.z > bmin.z) o.z = o.z / (bmax.z - bmin.z);
+    int pi0 = int(o.x * float(S.light_nv[0])), pi1 = int(o.y * float(S.light_nv[1])), pi2 = int(o.z * float(S.light_nv[2]));
+    pi0 = pi0 < 0 ? 0 : (pi0 > S.light_nv[0] - 1 ? S.light_nv[0] - 1 : pi0);
+    pi1 = pi1 < 0 ? 0 : (pi1 > S.light_nv[1] - 1 ? S.light_nv[1] - 1 : pi1);
+    pi2 = pi2 < 0 ? 0 : (pi2 > S.light_nv[2] - 1 ? S.light_nv[2] - 1 : pi2);
+    const int n = S.n_lights, size = n + 1;
+    const float *d = S.light_dist + uint32_t((pi0 * S.light_nv[1] + pi1) * S.light_nv[2] + pi2) * light_record_floats(n);
+    const float *cdf = d + n;
+    int first = 0, len = size;
+    while (len > 0) {
+        const int half = len >> 1, middle = first + half;
+        if (cdf[middle] <= u) {
+            first = middle + 1;
+            len -= half + 1;
+        } else
+            len = half;
+    }
+    int offset = first - 1;
+    offset = offset < 0 ? 0 : (offset > size - 2 ? size - 2 : offset);
+    const float func_int = d[2 * n + 1];
+    *pdf = (func_int > 0) ? d[offset] / (func_int * float(n)) : 0.f;
+    return offset;
+}

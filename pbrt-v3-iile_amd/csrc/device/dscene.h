@@ -111,8 +111,9 @@ constexpr int kMaxHaltonDims = 128;
 constexpr int kMaxSpheres = 8;
 constexpr int kMaxQuadrics = 1024;  // = IILE_MAX_QUADRICS (checked in api_scene.hip)
 constexpr int kMaxMaterials = 64;
-constexpr int kMaxLights = 8;
-constexpr int kLightDistStride = 2 * kMaxLights + 2;  // a light distribution: func[kMaxLights], cdf[kMaxLights + 1], funcInt
+// (lights: as many as the scene has. One Distribution1D over them is a record func[n] | cdf[n + 1] | funcInt of
+//  2 n + 2 floats; the spatial strategy's table of them is capped in bytes — under 2^28 floats — in api_scene.hip)
+constexpr uint32_t light_record_floats(int n_lights) { return 2u * uint32_t(n_lights) + 2u; }
 
 // One IISPT probe camera (HemisphericCamera, hemispheric.cpp:109-160): CameraToWorld and the rows that transform a
 // world normal into the camera's frame (transpose of WorldToCamera's mInv, transform.h:243-249)
@@ -165,7 +166,8 @@ struct DScene {
     const float4 *top4;
     int n_top;
     int root_ref_top;         // root_ref, or kTopFlag | 0 when the root record is among them
-    // SpatialLightDistribution (n_lights > 1): per voxel {func[kMaxLights], cdf[kMaxLights + 1], funcInt}
+    // SpatialLightDistribution (n_lights > 1): per voxel {func[n_lights], cdf[n_lights + 1], funcInt}, 2 n_lights + 2 floats
+    // (light_record_floats); the uniform and power strategies: one such record, a grid of one voxel
     const float *light_dist;
     int light_nv[3];
     int has_infinite;         // some light is an InfiniteAreaLight: escaped rays carry radiance (k_miss)
@@ -222,7 +224,7 @@ struct DScene {
 // BSDF-sampled ray can matter have one):
 //   n2 = (mis o.xyz, bitcast record slot)   n3 = (mis d.xyz, bitcast light)
 // plus a byte plane written by k_mis / k_mis_lit, indexed by record slot:
-// nee_mis (area light index + 1 of the primitive the MIS ray ended on, 0 = none; then 1 = lit)
+// nee_mis (1: the MIS ray ended on an emitting primitive, left in mis_hit; 255: it escaped; 0: neither; then 1 = lit)
 enum { NEE_HAS_SHADOW = 1, NEE_HAS_MIS = 2 };
 
 struct DCounters {

@@ -129,9 +129,10 @@ struct Trav {
     float b0, b1, b2;  // barycentrics of the closest triangle hit (t itself is t.tmax)
 };
 // The vertex record's flag word carries the primitive's shading class (bits 5..7: material
-// type, +4 for a sphere) and its (area light index + 1) (bits 8..11). Both ride along in
-// hit_prim bits 24..30, so that extend can tag shade-queue entries with the class and the
-// MIS kernel knows whether its ray ended on an emitter, without fetching the primitive again.
+// type, +4 for a sphere) and whether it is an area light (bit 8; bits 9..11 are clear; WHICH light
+// is the record's third word). Both ride along in hit_prim bits 24..30, so that extend can tag
+// shade-queue entries with the class and the MIS kernel knows whether its ray ended on an emitter,
+// without fetching the primitive again.
 constexpr int kHitClassShift = 24;
 constexpr int kHitLightShift = 27;
 constexpr int kHitPrimMask = (1 << kHitClassShift) - 1;

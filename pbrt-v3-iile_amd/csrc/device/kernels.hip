@@ -93,8 +93,8 @@ __global__ __launch_bounds__(kBlock) void k_miss(DScene S, PassBuffers B, int bo
     }
 }
 
-// mis_lit: k_mis leaves, per record, the (area light index + 1) of the primitive its MIS ray
-// ended on. This pass over that byte plane turns it into "the ray reached the *sampled* light,
+// mis_lit: k_mis leaves, per record, whether its MIS ray ended on an emitting primitive (1, the hit in
+// mis_hit), escaped (255) or neither (0). This pass over that byte plane turns it into "the ray reached the *sampled* light,
 // on its emitting side" (`lightIsect.primitive->GetAreaLight() == &light`, then
 // SurfaceInteraction::Le -> DiffuseAreaLight::L; integrator.cpp:205-209). Only the rare records
 // whose ray did end on an emitter are looked at any further.
@@ -111,9 +111,12 @@ __global__ __launch_bounds__(kBlock) void k_mis_lit(DScene S, PassBuffers B, int
         bool lit = false;
         if (mis == 255u) {
             lit = S.lights[li].type == kLightInfinite;  // `else Li = light.Le(ray)`, integrator.cpp:209-210
-        } else if (int(mis) == li + 1) {
+        } else {
             const float4 h4 = B.mis_hit[e];  // left by k_mis
-            lit = mis_ray_lit(S, li, int(f2b(h4.x)), h4.y, h4.z, h4.w, F3{n2.x, n2.y, n2.z}, F3{n3.x, n3.y, n3.z});
+            const int prim = int(f2b(h4.x));
+            // which light the primitive is: the third word of its vertex record (the flag word says only that it is one)
+            if (int(f2b(S.tri_verts[3 * size_t(prim) + 2].w)) == li)
+                lit = mis_ray_lit(S, li, prim, h4.y, h4.z, h4.w, F3{n2.x, n2.y, n2.z}, F3{n3.x, n3.y, n3.z});
         }
         B.nee_mis[e] = lit ? 1 : 0;
     }
@@ -771,6 +774,19 @@ __global__ void k_light_probe(DScene S, int n, int light, const float *p, float 
 }
 void launch_light_probe(const DScene &S, int n, int light, const float *p, float *out, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_light_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, light, p, out);
+}
+// the light k_shade samples at point p with the 1D sample u, and the pdf of that choice (UniformSampleOneLight, integrator.cpp:85-106)
+__global__ void k_light_choose(DScene S, int n, const float *p, const float *u, int *light, float *pdf) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int li = 0;
+    float sel = 1.f;
+    if (S.n_lights > 1) li = sample_light(S, F3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}, u[i], &sel);
+    light[i] = li;
+    pdf[i] = sel;
+}
+void launch_light_choose(const DScene &S, int n, const float *p, const float *u, int *light, float *pdf, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_light_choose, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, p, u, light, pdf);
 }
 void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, const float *pdp, float *out,
                           const LaunchCfg &cfg) {

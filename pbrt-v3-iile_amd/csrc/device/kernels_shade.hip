@@ -10,7 +10,7 @@ namespace iile {
 // SpatialLightDistribution (core/lightdistrib.cpp:91-299): with more than one light the path
 // integrator picks the light to sample from a per-voxel distribution. The reference fills a
 // hash table lazily; a voxel's distribution is a pure function of its index, so all of them are
-// tabulated once at scene creation (k_light_distributions) and looked up densely.
+// tabulated once at scene creation (k_light_contrib, k_light_cdf) and looked up densely (sample_light, dlight.h).
 // Light::Sample_Li at an Interaction without normal or error bounds (lightdistrib.cpp:258-262)
 DEV F3 sample_li_plain(const DScene &S, const DLight &lt, F3 po, float u0, float u1, float *pdf) {
     *pdf = 1;
@@ -35,88 +35,58 @@ DEV F3 sample_li_plain(const DScene &S, const DLight &lt, F3 po, float u0, float
     return area_light_L(lt, ps.n, -wi);
 }
 DEV float lerp_f(float t, float a, float b) { return (1 - t) * a + t * b; }  // pbrt.h:414
-// SpatialLightDistribution::ComputeDistribution (lightdistrib.cpp:228-299), one thread per voxel.
-// samples: RadicalInverse(0..4, i) for i < 128 (host table)
-__global__ void k_light_distributions(DScene S, const float *samples, float *out) {
+// SpatialLightDistribution::ComputeDistribution (lightdistrib.cpp:228-299) in two kernels over the table of `stride` = 2 n + 2
+// floats per voxel. samples: RadicalInverse(0..4, i) for i < 128 (host table).
+// k_light_contrib: one thread per (voxel, light) — blockIdx.y is the light, so a wavefront's lanes share it and sample_li_plain's
+// switch on the light's type is wave-uniform. Its 128 samples in order; the sum goes to the record's func[light] slot.
+__global__ __launch_bounds__(128) void k_light_contrib(DScene S, const float *samples, float *out, uint32_t stride) {
     const int nv0 = S.light_nv[0], nv1 = S.light_nv[1], nv2 = S.light_nv[2];
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= nv0 * nv1 * nv2) return;
+    const int v = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+    if (v >= nv0 * nv1 * nv2 || j >= S.n_lights) return;
     const int pi2 = v % nv2, pi1 = (v / nv2) % nv1, pi0 = v / (nv2 * nv1);
     const F3 bmin = F3{S.root_box[0], S.root_box[1], S.root_box[2]}, bmax = F3{S.root_box[3], S.root_box[4], S.root_box[5]};
     const F3 p0 = F3{float(pi0) / float(nv0), float(pi1) / float(nv1), float(pi2) / float(nv2)};
     const F3 p1 = F3{float(pi0 + 1) / float(nv0), float(pi1 + 1) / float(nv1), float(pi2 + 1) / float(nv2)};
     const F3 vmin = F3{lerp_f(p0.x, bmin.x, bmax.x), lerp_f(p0.y, bmin.y, bmax.y), lerp_f(p0.z, bmin.z, bmax.z)};
     const F3 vmax = F3{lerp_f(p1.x, bmin.x, bmax.x), lerp_f(p1.y, bmin.y, bmax.y), lerp_f(p1.z, bmin.z, bmax.z)};
-    const int n = S.n_lights;
-    float contrib[kMaxLights];
-#pragma unroll
-    for (int j = 0; j < kMaxLights; ++j) contrib[j] = 0;
+    const DLight &lt = S.lights[j];
+    float contrib = 0;
     for (int i = 0; i < 128; ++i) {
         const float *t = samples + 5 * i;
         const F3 po = F3{lerp_f(t[0], vmin.x, vmax.x), lerp_f(t[1], vmin.y, vmax.y), lerp_f(t[2], vmin.z, vmax.z)};
-#pragma unroll
-        for (int j = 0; j < kMaxLights; ++j) {
-            if (j < n) {
-                float pdf;
-                const F3 Li = sample_li_plain(S, S.lights[j], po, t[3], t[4], &pdf);
-                if (pdf > 0) contrib[j] += lum_y(Li) / pdf;
-            }
-        }
+        float pdf;
+        const F3 Li = sample_li_plain(S, lt, po, t[3], t[4], &pdf);
+        if (pdf > 0) contrib += lum_y(Li) / pdf;
     }
+    out[size_t(v) * stride + size_t(j)] = contrib;
+}
+// k_light_cdf: one thread per voxel turns the contributions k_light_contrib left in func[] into the Distribution1D — the sum in
+// light order, the floor of a thousandth of the average, the running cdf and its normalisation (sampling.h:57-69).
+__global__ __launch_bounds__(128) void k_light_cdf(DScene S, float *out) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= S.light_nv[0] * S.light_nv[1] * S.light_nv[2]) return;
+    const int n = S.n_lights;
+    float *d = out + size_t(v) * light_record_floats(n);
     float sum = 0;
-#pragma unroll
-    for (int j = 0; j < kMaxLights; ++j)
-        if (j < n) sum = sum + contrib[j];
+    for (int j = 0; j < n; ++j) sum = sum + d[j];
     const float avg = sum / float(128 * n);
     const float min_contrib = (avg > 0) ? float(.001 * double(avg)) : 1.f;
-    float *d = out + size_t(v) * kLightDistStride;
     float cdf = 0;
-    d[kMaxLights] = 0;
-#pragma unroll
-    for (int j = 0; j < kMaxLights; ++j) {
-        if (j < n) {
-            const float f = mx(contrib[j], min_contrib);
-            d[j] = f;
-            cdf = cdf + f / float(n);
-            d[kMaxLights + 1 + j] = cdf;
-        }
+    d[n] = 0;
+    for (int j = 0; j < n; ++j) {
+        const float f = mx(d[j], min_contrib);
+        d[j] = f;
+        cdf = cdf + f / float(n);
+        d[n + 1 + j] = cdf;
     }
     const float func_int = cdf;
-    d[2 * kMaxLights + 1] = func_int;
+    d[2 * n + 1] = func_int;
     for (int i = 1; i < n + 1; ++i) {
         if (func_int == 0)
-            d[kMaxLights + i] = float(i) / float(n);
+            d[n + i] = float(i) / float(n);
         else
-            d[kMaxLights + i] = d[kMaxLights + i] / func_int;
+            d[n + i] = d[n + i] / func_int;
     }
-}
-// SpatialLightDistribution::Lookup + Distribution1D::SampleDiscrete (sampling.h:90-100, FindInterval pbrt.h:399-412)
-DEV int sample_light(const DScene &S, F3 p, float u, float *pdf) {
-    const F3 bmin = F3{S.root_box[0], S.root_box[1], S.root_box[2]}, bmax = F3{S.root_box[3], S.root_box[4], S.root_box[5]};
-    F3 o = p - bmin;  // Bounds3::Offset, geometry.h:800-806
-    if (bmax.x > bmin.x) o.x = o.x / (bmax.x - bmin.x);
-    if (bmax.y > bmin.y) o.y = o.y / (bmax.y - bmin.y);
-    if (bmax.z > bmin.z) o.z = o.z / (bmax.z - bmin.z);
-    int pi0 = int(o.x * float(S.light_nv[0])), pi1 = int(o.y * float(S.light_nv[1])), pi2 = int(o.z * float(S.light_nv[2]));
-    pi0 = pi0 < 0 ? 0 : (pi0 > S.light_nv[0] - 1 ? S.light_nv[0] - 1 : pi0);
-    pi1 = pi1 < 0 ? 0 : (pi1 > S.light_nv[1] - 1 ? S.light_nv[1] - 1 : pi1);
-    pi2 = pi2 < 0 ? 0 : (pi2 > S.light_nv[2] - 1 ? S.light_nv[2] - 1 : pi2);
-    const float *d = S.light_dist + size_t((pi0 * S.light_nv[1] + pi1) * S.light_nv[2] + pi2) * kLightDistStride;
-    const int n = S.n_lights, size = n + 1;
-    int first = 0, len = size;
-    while (len > 0) {
-        const int half = len >> 1, middle = first + half;
-        if (d[kMaxLights + middle] <= u) {
-            first = middle + 1;
-            len -= half + 1;
-        } else
-            len = half;
-    }
-    int offset = first - 1;
-    offset = offset < 0 ? 0 : (offset > size - 2 ? size - 2 : offset);
-    const float func_int = d[2 * kMaxLights + 1];
-    *pdf = (func_int > 0) ? d[offset] / (func_int * float(n)) : 0.f;
-    return offset;
 }
 
 // shade: one bounce of PathIntegrator::Li (path.cpp:81-191) for every hit of the
@@ -486,7 +456,16 @@ void launch_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int 
 }
 void launch_light_distributions(const DScene &S, const float *samples, float *out, const LaunchCfg &cfg) {
     const int n = S.light_nv[0] * S.light_nv[1] * S.light_nv[2];
-    hipLaunchKernelGGL(k_light_distributions, dim3((n + 127) / 128), dim3(128), 0, cfg.stream, S, samples, out);
+    // (lights ride in the grid's y: at most 65535 of them; the table's byte cap admits far fewer on any grid of more than 64 voxels,
+    //  and the loop covers the flat grids)
+    for (int l0 = 0; l0 < S.n_lights; l0 += 32768) {
+        DScene part = S;
+        part.lights = S.lights + l0;
+        part.n_lights = std::min(S.n_lights - l0, 32768);
+        hipLaunchKernelGGL(k_light_contrib, dim3((n + 127) / 128, part.n_lights), dim3(128), 0, cfg.stream, part, samples, out + l0,
+                           light_record_floats(S.n_lights));
+    }
+    hipLaunchKernelGGL(k_light_cdf, dim3((n + 127) / 128), dim3(128), 0, cfg.stream, S, out);
 }
 
 }  // namespace iile

@@ -301,8 +301,8 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_mis(DScene S, P
         trav_wave_step<COUNT, ALPHA, ANYORDER>(S, active, t, sr, &st, false, &B.nee[3 * size_t(plane) + q]);
         if (first_hit_ends && active && t.hit_prim >= 0) t.have = false;
         if (active && !t.have) {
-            // store only: (area light index + 1) of the primitive the MIS ray ended on, 0 for none
-            // 255: the ray escaped (matters to an infinite light only)
+            // store only: 1 when the primitive the MIS ray ended on is an emitter (the "is a light" bit of its flag word, carried
+            // in the hit's tag), 0 for none; 255: the ray escaped (matters to an infinite light only)
             const uint8_t on_light = uint8_t(t.hit_prim < 0 ? (S.has_infinite ? 255 : 0) : (t.hit_prim >> kHitLightShift));
             B.nee_mis[e] = on_light;
             // the rare ray that ends on an emitter leaves its hit for k_mis_lit (the hit records are

@@ -338,8 +338,10 @@ bool finalize_scene(HostScene *s, std::string *err) {
     }
     d.integrator.light_strategy = s->light_strategy == "uniform" ? IILE_LIGHTS_UNIFORM : (s->light_strategy == "power" ? IILE_LIGHTS_POWER : IILE_LIGHTS_SPATIAL);
     // Light::Power().y() of every light (ComputeLightPowerDistribution, integrator.cpp:217-225)
+    // of all of them in light_power_all, of the first IILE_MAX_LIGHTS in the integrator's own array too
     for (int i = 0; i < IILE_MAX_LIGHTS; ++i) d.integrator.light_power[i] = 0;
-    for (size_t i = 0; i < s->lights.size() && i < size_t(IILE_MAX_LIGHTS); ++i) {
+    s->light_power_all.assign(s->lights.size(), 0.f);
+    for (size_t i = 0; i < s->lights.size(); ++i) {
         const iile_light &lt = s->lights[i];
         float pw[3] = {0, 0, 0};
         const float wr = lt.world_radius;
@@ -383,8 +385,10 @@ bool finalize_scene(HostScene *s, std::string *err) {
             }
             }
         }
-        d.integrator.light_power[i] = 0.212671f * pw[0] + 0.715160f * pw[1] + 0.072169f * pw[2];
+        s->light_power_all[i] = 0.212671f * pw[0] + 0.715160f * pw[1] + 0.072169f * pw[2];
+        if (i < size_t(IILE_MAX_LIGHTS)) d.integrator.light_power[i] = s->light_power_all[i];
     }
+    d.light_power_all = s->light_power_all.data();
 
     // IISPT probe pass: CreateHemisphericCamera's film (hemispheric.cpp:131-147) and CreateIISPTdIntegrator's
     // sampler and depth (iispt_d.cpp:492-527)

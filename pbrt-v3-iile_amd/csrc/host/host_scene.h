@@ -79,6 +79,7 @@ struct HostScene {
     std::vector<int32_t> primes, prime_sums;
     std::vector<uint32_t> sobol_matrices;  // [n_dims][32] when the sampler is "sobol"
     std::vector<float> env_dist;  // Distribution2D tables of the infinite lights
+    std::vector<float> light_power_all;  // Power().y() of every light (iile_scene_desc::light_power_all)
     std::vector<iile_texture> o_textures;
     std::vector<float> o_texels;
     int n_interior = 0, n_leaf = 0;
