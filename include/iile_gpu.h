@@ -351,6 +351,17 @@ void iile_traversal_limits(int32_t *out3);
 /* Light::Sample_Li of delta light `light` (point, spot, distant, projection, goniometric: iile_light_is_delta; any other is
  * IILE_ERR_ARG) at n points p3, each an Interaction without a surface: out7 = {wi.xyz, Li.rgb, pdf} per point. */
 int iile_light_sample_li(iile_scene *scene, int32_t light, int32_t n, const float *p3, float *out7);
+/* Light::Sample_Li of area light (on a sphere, a triangle, a disk or a cylinder) or infinite light `light` (any other is
+ * IILE_ERR_ARG; delta lights: iile_light_sample_li) at n reference Interactions with point ref_p3, normal ref_n3 (zero: a point
+ * without a surface) and no error bounds, with the 2D samples u2: out13 = {wi.xyz, Li.rgb, pdf, p_light.xyz, n_light.xyz} per
+ * point. Area lights: Shape::Sample(ref, u), then the wi, pdf == 0 and L steps of DiffuseAreaLight::Sample_Li; p_light and n_light
+ * are the sampled Interaction's. The infinite light: p_light is the shadow ray's target, n_light is zero. */
+int iile_light_sample_at(iile_scene *scene, int32_t light, int32_t n, const float *ref_p3, const float *ref_n3, const float *u2, float *out13);
+/* Light::Pdf_Li of the same lights for the reference Interactions above and directions wi3: Shape::Pdf(ref, wi), or
+ * InfiniteAreaLight::Pdf_Li(wi) (which reads no reference point). */
+int iile_light_pdf_at(iile_scene *scene, int32_t light, int32_t n, const float *ref_p3, const float *ref_n3, const float *wi3, float *out_pdf);
+/* InfiniteAreaLight::Le for the directions d3 of n escaped rays; any other light type is IILE_ERR_ARG. */
+int iile_light_le(iile_scene *scene, int32_t light, int32_t n, const float *d3, float *out3);
 /* The light the path integrator's UniformSampleOneLight samples at each of n points p3 with the 1D sample u[i], and the pdf of
  * that choice, under the scene's "lightsamplestrategy" (LightDistribution::Lookup + Distribution1D::SampleDiscrete,
  * integrator.cpp:85-106). A scene of one light: light 0 with pdf 1. Queued on `stream` (NULL: the null stream), which is drained

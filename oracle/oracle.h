@@ -159,6 +159,15 @@ void oracle_sphere_solid_angle(const iile_scene_desc *scene, int sphere, const f
  * points, and by uniform-direction Monte Carlo with the same points. */
 int oracle_light_solid_angle(const iile_scene_desc *scene, int light, const float *p3, int n_samples,
                               double *by_sampling, double *by_uniform_directions);
+/* The sampled lights function by function, in portable-trig mode, with the arguments and outputs of the device's
+ * iile_light_sample_at / iile_light_pdf_at / iile_light_le (include/iile_gpu.h): Shape::Sample(ref, u) with the wi, pdf == 0 and L
+ * steps of DiffuseAreaLight::Sample_Li, Shape::Pdf(ref, wi), and InfiniteAreaLight::Sample_Li / Pdf_Li / Le. A sphere, a triangle or
+ * the infinite light; a scene with quadrics is ORACLE_UNSUPPORTED_*, any other light (or a light number out of range) returns 1. */
+int oracle_light_sample_at(const iile_scene_desc *scene, int light, int n, const float *ref_p3, const float *ref_n3, const float *u2,
+                           float *out13);
+int oracle_light_pdf_at(const iile_scene_desc *scene, int light, int n, const float *ref_p3, const float *ref_n3, const float *wi3,
+                        float *out_pdf);
+int oracle_light_le(const iile_scene_desc *scene, int light, int n, const float *d3, float *out3);
 int64_t oracle_check_next_float(int iters, uint64_t seed);
 int64_t oracle_check_efloat(int iters, uint64_t seed);
 int64_t oracle_check_reintersect(const iile_scene_desc *scene, int n, const float *o, const float *d, int n_out,

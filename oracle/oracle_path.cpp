@@ -2537,11 +2537,11 @@ struct Oracle {
         float p = trig.atan2_f(v.y, v.x);
         return (p < 0) ? (p + 2 * Pi) : p;
     }
-    Rgb inf_le(const iile_light &lt, V3 d) const {  // InfiniteAreaLight::Le, infinite.cpp:99-104
+    Rgb inf_le(const iile_light &lt, V3 d) const {  // InfiniteAreaLight::Le, infinite.cpp:92-96
         V3 w = normalize(inf_w2l(lt, d));
         return inf_lookup(lt, spherical_phi(w) * Inv2Pi, spherical_theta(w) * InvPi);
     }
-    Rgb inf_sample_li(const iile_light &lt, V3 ref_p, const float *u, V3 *wi, float *pdf, V3 *target) const {  // :106-137
+    Rgb inf_sample_li(const iile_light &lt, V3 ref_p, const float *u, V3 *wi, float *pdf, V3 *target) const {  // :98-122
         float pdfs[2];
         int v;
         float d1 = dist1d_sample(inf_marg(lt), lt.dist_h, u[1], &pdfs[1], &v);
@@ -2560,14 +2560,19 @@ struct Oracle {
         *target = ref_p + *wi * (2 * lt.world_radius);
         return inf_lookup(lt, d0, d1);
     }
-    float inf_pdf_li(const iile_light &lt, V3 w) const {  // :139-148
+    float inf_pdf_li(const iile_light &lt, V3 w) const {  // :124-132
         V3 wi = inf_w2l(lt, w);
         float theta = spherical_theta(wi), phi = spherical_phi(wi);
         float sin_theta = trig.sin_f(theta);
-        if (sin_theta == 0) return 0;
+        // :129 tests sinTheta == 0, which float32 meets at +z only: acos(-1) is the float above pi, whose sine is -8.7e-8, and the
+        // pdf came out negative there. Both poles return 0.
+        if (sin_theta <= 0) return 0;
+        // an all-black map: Distribution2D::Pdf would be 0 / 0. Sample_Li never returns a direction then (mapPdf == 0): the pdf is 0
+        const float func_int = inf_marg(lt)[2 * lt.dist_h + 1];
+        if (!(func_int > 0)) return 0;
         float p0 = phi * Inv2Pi, p1 = theta * InvPi;  // Distribution2D::Pdf, sampling.h:135-142
         int iu = std::min(std::max(int(p0 * lt.dist_w), 0), lt.dist_w - 1), iv = std::min(std::max(int(p1 * lt.dist_h), 0), lt.dist_h - 1);
-        return (inf_cond(lt, iv)[iu] / inf_marg(lt)[2 * lt.dist_h + 1]) / (2 * Pi * Pi * sin_theta);
+        return (inf_cond(lt, iv)[iu] / func_int) / (2 * Pi * Pi * sin_theta);
     }
     // EstimateDirect for the infinite light: both halves, with Le(ray) where the BSDF-sampled ray escapes
     Rgb estimate_direct_infinite(const Isect &it, const Bsdf &bsdf, const float *u_scatter, const iile_light &lt,
@@ -4083,6 +4088,82 @@ int oracle_light_solid_angle(const iile_scene_desc *scene, int light, const floa
     }
     *by_sampling = sa;
     *by_uniform_directions = hits / (double(n_samples) * (1.0 / (4 * 3.14159265358979323846)));
+    return 0;
+}
+
+// The sampled lights one function at a time (oracle.h): shape_sample / shape_pdf / inf_sample_li / inf_pdf_li / inf_le as the
+// integrators call them, with the portable trigonometry the device evaluates.
+namespace {
+int check_sampled_light(const iile_scene_desc &S, int light) {
+    if (light < 0 || light >= S.n_lights) return 1;
+    if (int rc = check_geometry(S)) return rc;
+    const int type = S.lights[light].type;
+    return (type == IILE_LIGHT_DIFFUSE_AREA || type == IILE_LIGHT_AREA_TRIANGLE || type == IILE_LIGHT_INFINITE) ? 0 : 1;
+}
+Isect light_ref(const float *p3, const float *n3, int i) {  // an Interaction with the given normal and pError = 0
+    Isect ref;
+    ref.p = V3(p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]);
+    ref.perr = V3(0, 0, 0);
+    ref.n = V3(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]);
+    return ref;
+}
+}  // namespace
+
+int oracle_light_sample_at(const iile_scene_desc *scene, int light, int n, const float *ref_p3, const float *ref_n3, const float *u2,
+                           float *out13) {
+    if (int rc = check_sampled_light(*scene, light)) return rc;
+    Counters c;
+    Oracle orc(*scene, ORACLE_TRIG_PORTABLE, &c);
+    const iile_light &lt = scene->lights[light];
+    for (int i = 0; i < n; ++i) {
+        const Isect ref = light_ref(ref_p3, ref_n3, i);
+        V3 wi(0, 0, 0), pl(0, 0, 0), nl(0, 0, 0);
+        Rgb Li(0.f);
+        float pdf = 0;
+        if (lt.type == IILE_LIGHT_INFINITE) {
+            Li = orc.inf_sample_li(lt, ref.p, u2 + 2 * i, &wi, &pdf, &pl);
+        } else {  // DiffuseAreaLight::Sample_Li, lights/diffuse.cpp:68-81
+            Oracle::LightSample ps = orc.shape_sample(lt, ref, u2 + 2 * i, &pdf);
+            pl = ps.p, nl = ps.n;
+            if (pdf == 0 || length_sq(ps.p - ref.p) == 0) {
+                pdf = 0;
+            } else {
+                wi = normalize(ps.p - ref.p);
+                Li = Oracle::light_L(lt, ps.n, -wi);
+            }
+        }
+        float *r = out13 + 13 * size_t(i);
+        r[0] = wi.x, r[1] = wi.y, r[2] = wi.z;
+        for (int k = 0; k < 3; ++k) r[3 + k] = Li.c[k];
+        r[6] = pdf;
+        r[7] = pl.x, r[8] = pl.y, r[9] = pl.z;
+        r[10] = nl.x, r[11] = nl.y, r[12] = nl.z;
+    }
+    return 0;
+}
+
+int oracle_light_pdf_at(const iile_scene_desc *scene, int light, int n, const float *ref_p3, const float *ref_n3, const float *wi3,
+                        float *out_pdf) {
+    if (int rc = check_sampled_light(*scene, light)) return rc;
+    Counters c;
+    Oracle orc(*scene, ORACLE_TRIG_PORTABLE, &c);
+    const iile_light &lt = scene->lights[light];
+    for (int i = 0; i < n; ++i) {
+        const V3 wi(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]);
+        out_pdf[i] = lt.type == IILE_LIGHT_INFINITE ? orc.inf_pdf_li(lt, wi) : orc.shape_pdf(lt, light_ref(ref_p3, ref_n3, i), wi);
+    }
+    return 0;
+}
+
+int oracle_light_le(const iile_scene_desc *scene, int light, int n, const float *d3, float *out3) {
+    if (int rc = check_sampled_light(*scene, light)) return rc;
+    if (scene->lights[light].type != IILE_LIGHT_INFINITE) return 1;
+    Counters c;
+    Oracle orc(*scene, ORACLE_TRIG_PORTABLE, &c);
+    for (int i = 0; i < n; ++i) {
+        Rgb L = orc.inf_le(scene->lights[light], V3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]));
+        for (int k = 0; k < 3; ++k) out3[3 * i + k] = L.c[k];
+    }
     return 0;
 }
 

@@ -226,7 +226,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
-               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_bsdf_sample_specular", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_light_choose", "iile_render_probes",
+               "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_bsdf_sample_specular", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_light_sample_at", "iile_light_pdf_at", "iile_light_le", "iile_light_choose", "iile_render_probes",
                "iile_render_probes_reference", "iile_test_probe_ref_group", "iile_reference_points",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
                "iile_stream_create", "iile_stream_wait", "iile_stream_destroy",
@@ -345,6 +345,9 @@ def gpu_lib():
         lib.iile_bsdf_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_texture_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_light_sample_li.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp]
+        lib.iile_light_sample_at.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
+        lib.iile_light_pdf_at.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
+        lib.iile_light_le.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp]
         lib.iile_light_choose.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         lib.iile_texture_eval_p.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         lib.iile_render_probes.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, ctypes.POINTER(GpuStats), c_vp]
@@ -779,6 +782,32 @@ class GpuScene:
         p = _f32(p).reshape(-1, 3)
         out = np.empty((len(p), 7), np.float32)
         self._check(gpu_lib().iile_light_sample_li(self._s, int(light), len(p), p.ctypes.data, out.ctypes.data), "iile_light_sample_li")
+        return out
+
+    def light_sample_at(self, light, ref_p, ref_n, u):
+        """Light::Sample_Li of area or infinite light `light` at the (n, 3) reference points ref_p with normals ref_n (zero: no
+        surface) and the (n, 2) samples u: (n, 13) {wi.xyz, Li.rgb, pdf, p_light.xyz, n_light.xyz}."""
+        ref_p, ref_n, u = _f32(ref_p).reshape(-1, 3), _f32(ref_n).reshape(-1, 3), _f32(u).reshape(-1, 2)
+        assert len(ref_p) == len(ref_n) == len(u)
+        out = np.empty((len(ref_p), 13), np.float32)
+        self._check(gpu_lib().iile_light_sample_at(self._s, int(light), len(ref_p), ref_p.ctypes.data, ref_n.ctypes.data, u.ctypes.data,
+                                                   out.ctypes.data), "iile_light_sample_at")
+        return out
+
+    def light_pdf_at(self, light, ref_p, ref_n, wi):
+        """Light::Pdf_Li of area or infinite light `light` for the (n, 3) reference points, normals and directions wi: (n,)."""
+        ref_p, ref_n, wi = _f32(ref_p).reshape(-1, 3), _f32(ref_n).reshape(-1, 3), _f32(wi).reshape(-1, 3)
+        assert len(ref_p) == len(ref_n) == len(wi)
+        out = np.empty(len(ref_p), np.float32)
+        self._check(gpu_lib().iile_light_pdf_at(self._s, int(light), len(ref_p), ref_p.ctypes.data, ref_n.ctypes.data, wi.ctypes.data,
+                                                out.ctypes.data), "iile_light_pdf_at")
+        return out
+
+    def light_le(self, light, d):
+        """InfiniteAreaLight::Le of infinite light `light` for the (n, 3) directions d of escaped rays: (n, 3)."""
+        d = _f32(d).reshape(-1, 3)
+        out = np.empty((len(d), 3), np.float32)
+        self._check(gpu_lib().iile_light_le(self._s, int(light), len(d), d.ctypes.data, out.ctypes.data), "iile_light_le")
         return out
 
     def light_choose(self, p, u, stream=None):

@@ -156,6 +156,50 @@ int iile_light_sample_li(iile_scene *sc, int32_t light, int32_t n, const float *
     return finish(dout, out7, 7 * size_t(n));
 }
 
+// the lights iile_light_sample_at and iile_light_pdf_at take: the sampled ones
+static bool light_is_sampled(int type) {
+    return type == IILE_LIGHT_DIFFUSE_AREA || type == IILE_LIGHT_AREA_TRIANGLE || type == IILE_LIGHT_AREA_QUADRIC || type == IILE_LIGHT_INFINITE;
+}
+
+int iile_light_sample_at(iile_scene *sc, int32_t light, int32_t n, const float *ref_p3, const float *ref_n3, const float *u2, float *out13) {
+    if (!sc || n < 0 || !ref_p3 || !ref_n3 || !u2 || !out13 || light < 0 || light >= sc->ds.n_lights)
+        return api_fail(IILE_ERR_ARG, "iile_light_sample_at: bad argument");
+    if (!light_is_sampled(sc->light_types[size_t(light)])) return api_fail(IILE_ERR_ARG, "iile_light_sample_at: not an area or infinite light");
+    int rc = ensure_device();
+    if (rc) return rc;
+    DevBuf<float> dp, dn, du, dout;
+    if ((rc = dp.put(ref_p3, 3 * size_t(n))) || (rc = dn.put(ref_n3, 3 * size_t(n))) || (rc = du.put(u2, 2 * size_t(n))) ||
+        (rc = dout.alloc(13 * size_t(n))))
+        return rc;
+    if (n) launch_light_sample_probe(sc->ds, n, light, dp.p, dn.p, du.p, dout.p, probe_cfg(sc));
+    return finish(dout, out13, 13 * size_t(n));
+}
+
+int iile_light_pdf_at(iile_scene *sc, int32_t light, int32_t n, const float *ref_p3, const float *ref_n3, const float *wi3, float *out_pdf) {
+    if (!sc || n < 0 || !ref_p3 || !ref_n3 || !wi3 || !out_pdf || light < 0 || light >= sc->ds.n_lights)
+        return api_fail(IILE_ERR_ARG, "iile_light_pdf_at: bad argument");
+    if (!light_is_sampled(sc->light_types[size_t(light)])) return api_fail(IILE_ERR_ARG, "iile_light_pdf_at: not an area or infinite light");
+    int rc = ensure_device();
+    if (rc) return rc;
+    DevBuf<float> dp, dn, dw, dout;
+    if ((rc = dp.put(ref_p3, 3 * size_t(n))) || (rc = dn.put(ref_n3, 3 * size_t(n))) || (rc = dw.put(wi3, 3 * size_t(n))) ||
+        (rc = dout.alloc(size_t(n))))
+        return rc;
+    if (n) launch_light_pdf_probe(sc->ds, n, light, dp.p, dn.p, dw.p, dout.p, probe_cfg(sc));
+    return finish(dout, out_pdf, size_t(n));
+}
+
+int iile_light_le(iile_scene *sc, int32_t light, int32_t n, const float *d3, float *out3) {
+    if (!sc || n < 0 || !d3 || !out3 || light < 0 || light >= sc->ds.n_lights) return api_fail(IILE_ERR_ARG, "iile_light_le: bad argument");
+    if (sc->light_types[size_t(light)] != IILE_LIGHT_INFINITE) return api_fail(IILE_ERR_ARG, "iile_light_le: not an infinite light");
+    int rc = ensure_device();
+    if (rc) return rc;
+    DevBuf<float> dd, dout;
+    if ((rc = dd.put(d3, 3 * size_t(n))) || (rc = dout.alloc(3 * size_t(n)))) return rc;
+    if (n) launch_light_le_probe(sc->ds, n, light, dd.p, dout.p, probe_cfg(sc));
+    return finish(dout, out3, 3 * size_t(n));
+}
+
 int iile_light_choose(iile_scene *sc, int32_t n, const float *p3, const float *u, int32_t *out_light, float *out_pdf, void *stream) {
     if (!sc || n < 0 || !p3 || !u || !out_light || !out_pdf) return api_fail(IILE_ERR_ARG, "iile_light_choose: bad argument");
     if (sc->ds.n_lights < 1) return api_fail(IILE_ERR_ARG, "iile_light_choose: the scene has no light");

@@ -184,11 +184,11 @@ DEV float spherical_phi(F3 v) {
     const float p = atan2_f(v.y, v.x);
     return (p < 0) ? (p + 2 * kPi) : p;
 }
-DEV F3 inf_le(const DScene &S, const DLight &lt, F3 d) {  // InfiniteAreaLight::Le, infinite.cpp:99-104
+DEV F3 inf_le(const DScene &S, const DLight &lt, F3 d) {  // InfiniteAreaLight::Le, infinite.cpp:92-96
     const F3 w = normalize(inf_w2l(lt, d));
     return inf_lookup(S, lt, spherical_phi(w) * kInv2Pi, spherical_theta(w) * kInvPi);
 }
-DEV F3 inf_sample_li(const DScene &S, const DLight &lt, F3 ref_p, float u0, float u1, F3 *wi, float *pdf, F3 *target) {  // :106-137
+DEV F3 inf_sample_li(const DScene &S, const DLight &lt, F3 ref_p, float u0, float u1, F3 *wi, float *pdf, F3 *target) {  // :98-122
     float pdf0, pdf1;
     int v;
     const float d1 = dist1d_sample(inf_cond(S, lt, lt.dist_h), lt.dist_h, u1, &pdf1, &v);
@@ -208,18 +208,23 @@ DEV F3 inf_sample_li(const DScene &S, const DLight &lt, F3 ref_p, float u0, floa
     *target = ref_p + *wi * (2 * lt.world_radius);
     return inf_lookup(S, lt, d0, d1);
 }
-DEV float inf_pdf_li(const DScene &S, const DLight &lt, F3 w) {  // :139-148 with Distribution2D::Pdf, sampling.h:135-142
+DEV float inf_pdf_li(const DScene &S, const DLight &lt, F3 w) {  // :124-132 with Distribution2D::Pdf, sampling.h:135-142
     const F3 wi = inf_w2l(lt, w);
     const float theta = spherical_theta(wi), phi = spherical_phi(wi);
     float sin_theta, cos_theta;
     sincos_f(theta, &sin_theta, &cos_theta);
-    if (sin_theta == 0) return 0;
+    // :129 tests sinTheta == 0, which float32 meets at +z only: acos(-1) is the float above pi, whose sine is -8.7e-8, and the pdf
+    // came out negative there. Both poles return 0.
+    if (sin_theta <= 0) return 0;
+    // an all-black map: Distribution2D::Pdf would be 0 / 0. Sample_Li never returns a direction then (mapPdf == 0): the pdf is 0
+    const float func_int = inf_cond(S, lt, lt.dist_h)[2 * lt.dist_h + 1];
+    if (!(func_int > 0)) return 0;
     const float p0 = phi * kInv2Pi, p1 = theta * kInvPi;
     int iu = int(p0 * float(lt.dist_w)), iv = int(p1 * float(lt.dist_h));
     iu = iu < 0 ? 0 : (iu > lt.dist_w - 1 ? lt.dist_w - 1 : iu);
     iv = iv < 0 ? 0 : (iv > lt.dist_h - 1 ? lt.dist_h - 1 : iv);
     const float func = inf_cond(S, lt, iv)[iu];
-    return (func / inf_cond(S, lt, lt.dist_h)[2 * lt.dist_h + 1]) / (2 * kPi * kPi * sin_theta);
+    return (func / func_int) / (2 * kPi * kPi * sin_theta);
 }
 
 // Triangle emitter (shapes/triangle.cpp:546-579) through the generic Shape::Sample(ref, u) /

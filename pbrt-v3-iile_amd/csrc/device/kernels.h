@@ -229,6 +229,9 @@ void launch_trig_probe(int n, const float *x, float *out, const LaunchCfg &cfg);
 void launch_patch_pass(const DScene &S, const PassDesc &P, const PassBuffers &B, const FilmBuffers &F, const PatchDev &D, const LaunchCfg &cfg);
 void launch_patch_merge(const DScene &S, const PassDesc &P, const FilmBuffers &F, const PatchDev &D, const LaunchCfg &cfg);
 void launch_light_probe(const DScene &S, int n, int light, const float *p, float *out, const LaunchCfg &cfg);
+void launch_light_sample_probe(const DScene &S, int n, int light, const float *p, const float *nrm, const float *u, float *out, const LaunchCfg &cfg);
+void launch_light_pdf_probe(const DScene &S, int n, int light, const float *p, const float *nrm, const float *w, float *out, const LaunchCfg &cfg);
+void launch_light_le_probe(const DScene &S, int n, int light, const float *d, float *out, const LaunchCfg &cfg);
 void launch_light_choose(const DScene &S, int n, const float *p, const float *u, int *light, float *pdf, const LaunchCfg &cfg);
 void launch_texture_probe(const DScene &S, int n, int tex, const float *uv, const float *duv, const float *pdp, float *out,
                           const LaunchCfg &cfg);

@@ -775,6 +775,72 @@ __global__ void k_light_probe(DScene S, int n, int light, const float *p, float 
 void launch_light_probe(const DScene &S, int n, int light, const float *p, float *out, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_light_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, light, p, out);
 }
+// Light::Sample_Li of area light (sphere, triangle, quadric) or infinite light `light` for reference point i, an Interaction with
+// normal ref_n (zero: a point without a surface) and no error bounds, and the 2D sample u: {wi, Li, pdf, p_light, n_light} (test
+// probe; the caller checked the light's type). An area light: shape_sample, then the wi, pdf == 0 and L steps of
+// DiffuseAreaLight::Sample_Li as estimate_direct_request has them. The infinite light: p_light is the shadow ray's target, n_light 0.
+__global__ void k_light_sample_probe(DScene S, int n, int light, const float *p, const float *nrm, const float *u, float *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DLight &lt = S.lights[light];
+    Isect ref;
+    ref.p = F3{p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+    ref.perr = F3{0, 0, 0};
+    ref.n = F3{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]};
+    F3 wi = F3{0, 0, 0}, Li = F3{0, 0, 0}, pl = F3{0, 0, 0}, nl = F3{0, 0, 0};
+    float pdf = 0;
+    if (lt.type == kLightInfinite) {
+        Li = inf_sample_li(S, lt, ref.p, u[2 * i], u[2 * i + 1], &wi, &pdf, &pl);
+    } else {
+        const LightSample ps = shape_sample(S, lt, ref, u[2 * i], u[2 * i + 1], &pdf);
+        pl = ps.p, nl = ps.n;
+        if (pdf == 0 || length_sq(ps.p - ref.p) == 0) {
+            pdf = 0;
+        } else {
+            wi = normalize(ps.p - ref.p);
+            Li = area_light_L(lt, ps.n, -wi);
+        }
+    }
+    float *r = out + 13 * size_t(i);
+    r[0] = wi.x, r[1] = wi.y, r[2] = wi.z;
+    r[3] = Li.x, r[4] = Li.y, r[5] = Li.z;
+    r[6] = pdf;
+    r[7] = pl.x, r[8] = pl.y, r[9] = pl.z;
+    r[10] = nl.x, r[11] = nl.y, r[12] = nl.z;
+}
+void launch_light_sample_probe(const DScene &S, int n, int light, const float *p, const float *nrm, const float *u, float *out, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_light_sample_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, light, p, nrm, u, out);
+}
+// Light::Pdf_Li of the same lights for reference point i and direction wi: shape_pdf or inf_pdf_li (test probe)
+__global__ void k_light_pdf_probe(DScene S, int n, int light, const float *p, const float *nrm, const float *w, float *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DLight &lt = S.lights[light];
+    const F3 wi = F3{w[3 * i], w[3 * i + 1], w[3 * i + 2]};
+    if (lt.type == kLightInfinite) {
+        out[i] = inf_pdf_li(S, lt, wi);
+        return;
+    }
+    Isect ref;
+    ref.p = F3{p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+    ref.perr = F3{0, 0, 0};
+    ref.n = F3{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]};
+    unsigned long long n_tests = 0, n_hits = 0;
+    out[i] = shape_pdf(S, lt, ref, wi, &n_tests, &n_hits);
+}
+void launch_light_pdf_probe(const DScene &S, int n, int light, const float *p, const float *nrm, const float *w, float *out, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_light_pdf_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, light, p, nrm, w, out);
+}
+// InfiniteAreaLight::Le of infinite light `light` for the direction d of an escaped ray (test probe)
+__global__ void k_light_le_probe(DScene S, int n, int light, const float *d, float *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const F3 L = inf_le(S, S.lights[light], F3{d[3 * i], d[3 * i + 1], d[3 * i + 2]});
+    out[3 * i] = L.x, out[3 * i + 1] = L.y, out[3 * i + 2] = L.z;
+}
+void launch_light_le_probe(const DScene &S, int n, int light, const float *d, float *out, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_light_le_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, light, d, out);
+}
 // the light k_shade samples at point p with the 1D sample u, and the pdf of that choice (UniformSampleOneLight, integrator.cpp:85-106)
 __global__ void k_light_choose(DScene S, int n, const float *p, const float *u, int *light, float *pdf) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

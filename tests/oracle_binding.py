@@ -77,6 +77,9 @@ class Oracle:
         lib.oracle_log.argtypes = [ctypes.c_int, ctypes.c_float]
         lib.oracle_log.restype = ctypes.c_float
         lib.oracle_light_solid_angle.argtypes = [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]
+        lib.oracle_light_sample_at.argtypes = [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]
+        lib.oracle_light_pdf_at.argtypes = [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]
+        lib.oracle_light_le.argtypes = [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp]
         lib.oracle_sphere_solid_angle.argtypes = [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]
         lib.oracle_check_next_float.restype = ctypes.c_int64
         lib.oracle_check_next_float.argtypes = [ctypes.c_int, ctypes.c_uint64]
@@ -244,6 +247,33 @@ class Oracle:
         _check("oracle_light_solid_angle",
                self.lib.oracle_light_solid_angle(scene.desc, light, p.ctypes.data, n_samples, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    def _light_rc(self, entry, rc):
+        if _check(entry, rc):
+            raise RuntimeError(f"{entry}: not a sphere, triangle or infinite light of the scene")
+
+    def light_sample_at(self, scene, light, ref_p, ref_n, u):
+        """As GpuScene.light_sample_at: (n, 13) {wi, Li, pdf, p_light, n_light}, portable trigonometry."""
+        ref_p, ref_n, u = _f32(ref_p).reshape(-1, 3), _f32(ref_n).reshape(-1, 3), _f32(u).reshape(-1, 2)
+        assert len(ref_p) == len(ref_n) == len(u)
+        out = np.empty((len(ref_p), 13), np.float32)
+        self._light_rc("oracle_light_sample_at", self.lib.oracle_light_sample_at(scene.desc, int(light), len(ref_p), ref_p.ctypes.data,
+                                                                                 ref_n.ctypes.data, u.ctypes.data, out.ctypes.data))
+        return out
+
+    def light_pdf_at(self, scene, light, ref_p, ref_n, wi):
+        ref_p, ref_n, wi = _f32(ref_p).reshape(-1, 3), _f32(ref_n).reshape(-1, 3), _f32(wi).reshape(-1, 3)
+        assert len(ref_p) == len(ref_n) == len(wi)
+        out = np.empty(len(ref_p), np.float32)
+        self._light_rc("oracle_light_pdf_at", self.lib.oracle_light_pdf_at(scene.desc, int(light), len(ref_p), ref_p.ctypes.data,
+                                                                           ref_n.ctypes.data, wi.ctypes.data, out.ctypes.data))
+        return out
+
+    def light_le(self, scene, light, d):
+        d = _f32(d).reshape(-1, 3)
+        out = np.empty((len(d), 3), np.float32)
+        self._light_rc("oracle_light_le", self.lib.oracle_light_le(scene.desc, int(light), len(d), d.ctypes.data, out.ctypes.data))
+        return out
 
     def sphere_solid_angle(self, scene, sphere, p, n_samples):
         p = _f32(p)
