@@ -149,6 +149,19 @@ int iile_trace_any(iile_scene *scene, int32_t n, const float *o3, const float *d
  * SampleDimension(index, dim0 + d). */
 int iile_halton_samples(iile_scene *scene, int32_t n, const int32_t *px, const int32_t *py, const int32_t *k,
                         int32_t dim0, int32_t ndims, float *out, uint32_t *index_out);
+/* Test probe of the scene's sample table (the Halton sampler's values, tabulated per (pixel mod 128, k) at iile_scene_create): for
+ * sample k[i] of pixel (px[i], py[i]) out[8i ..] = the table's record of bounce[i] >= 0 — SampleDimension(index, 5 + 7 bounce + j),
+ * j < 8 — or, for bounce[i] < 0, its camera part {dimension 0, 1, 3, 4, 0, 0, 0, 0} (dimensions 3 and 4 are kept, else 0, when the
+ * lens is open). IILE_ERR_ARG: the scene has no table, k outside [0, pixelsamples), bounce >= maxdepth.
+ * iile_sample_table_budget: the byte budget the next iile_scene_create holds a table to: the constant (4 GiB) unless the test probe
+ * iile_test_sample_table_budget has set another for this process (0: the constant again). */
+int iile_sample_table_records(iile_scene *scene, int32_t n, const int32_t *px, const int32_t *py, const int32_t *k, const int32_t *bounce,
+                              float *out8);
+uint64_t iile_sample_table_budget(void);
+void iile_test_sample_table_budget(uint64_t bytes);
+/* HBM held by the scene's sample table; 0: the scene has none (Sobol', maxdepth 0, a table over its byte budget, IILE_NO_SAMPLE_TABLE
+ * set at iile_scene_create). The binding reports it with a render's statistics (iile_stats keeps its layout). */
+uint64_t iile_sample_table_bytes(const iile_scene *scene);
 /* PerspectiveCamera::GenerateRayDifferential or, for an environment camera, EnvironmentCamera::GenerateRay (origin /
  * direction only). plens may be NULL; the environment camera ignores it. */
 int iile_camera_rays(iile_scene *scene, int32_t n, const float *pfilm2, const float *plens2, float *o3, float *d3);

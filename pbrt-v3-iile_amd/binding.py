@@ -225,7 +225,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
-               "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_camera_rays", "iile_li_samples",
+               "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_sample_table_records", "iile_sample_table_budget", "iile_test_sample_table_budget", "iile_sample_table_bytes", "iile_camera_rays", "iile_li_samples",
                "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_bsdf_sample_specular", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_light_sample_at", "iile_light_pdf_at", "iile_light_le", "iile_light_choose", "iile_render_probes",
                "iile_render_probes_reference", "iile_test_probe_ref_group", "iile_reference_points",
                "iile_device_select", "iile_device_alloc", "iile_device_free", "iile_device_download", "iile_device_upload", "iile_device_zero",
@@ -370,6 +370,12 @@ def gpu_lib():
         lib.iile_traversal_limits.argtypes = [ctypes.POINTER(c_i32)]
         lib.iile_traversal_limits.restype = None
         lib.iile_test_patch_capacity.argtypes = [c_vp, c_u32]
+        lib.iile_sample_table_budget.argtypes = []
+        lib.iile_sample_table_budget.restype = c_u64
+        lib.iile_test_sample_table_budget.argtypes = [c_u64]
+        lib.iile_test_sample_table_budget.restype = None
+        lib.iile_sample_table_bytes.argtypes = [c_vp]
+        lib.iile_sample_table_bytes.restype = c_u64
         lib.iile_iispt_net_create.argtypes = [ctypes.POINTER(NetWeights), ctypes.POINTER(c_vp)]
         lib.iile_iispt_net_load.argtypes = [ctypes.c_char_p, ctypes.POINTER(c_vp)]
         lib.iile_iispt_net_forward.argtypes = [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32]
@@ -667,6 +673,16 @@ class HostScene:
             pass
 
 
+def sample_table_budget():
+    """iile_sample_table_budget: bytes the next GpuScene's table of Halton samples may take (a larger one is not built)."""
+    return int(gpu_lib().iile_sample_table_budget())
+
+
+def set_test_sample_table_budget(nbytes):
+    """iile_test_sample_table_budget: the budget of the scenes this process creates next; 0: the constant again."""
+    gpu_lib().iile_test_sample_table_budget(int(nbytes))
+
+
 class GpuScene:
     """Device-resident scene + wavefront integrator (libiile_gpu)."""
 
@@ -698,7 +714,11 @@ class GpuScene:
             ptr = film.ctypes.data
         rc = gpu_lib().iile_render(self._s, ctypes.byref(prm), ptr, ctypes.byref(st) if want_stats else None)
         self._check(rc, "iile_render")
-        return film, (st.as_dict() if want_stats else None)
+        if not want_stats:
+            return film, None
+        d = st.as_dict()
+        d["sample_table_bytes"] = int(gpu_lib().iile_sample_table_bytes(self._s))  # (not a field of iile_stats: its layout is pinned)
+        return film, d
 
     def render_status(self, stream=None):
         """iile_render_status: waits for `stream`; raises if the last asynchronous render's exact film finish overflowed."""
@@ -749,6 +769,17 @@ class GpuScene:
         self._check(gpu_lib().iile_halton_samples(self._s, n, px.ctypes.data, py.ctypes.data, k.ctypes.data, dim0,
                                                   ndims, out.ctypes.data, idx.ctypes.data), "iile_halton_samples")
         return out, idx
+
+    def sample_table_records(self, px, py, k, bounce):
+        """iile_sample_table_records: (n, 8) float32, the sample table's record of bounce[i] (dimensions 5 + 7 bounce ..) or, for
+        bounce[i] < 0, its camera part {dim 0, 1, 3, 4, 0, 0, 0, 0}, of sample k[i] of pixel (px[i], py[i])."""
+        px, py, k, bounce = _i32(px), _i32(py), _i32(k), _i32(bounce)
+        out = np.empty((len(px), 8), np.float32)
+        f = gpu_lib().iile_sample_table_records
+        f.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
+        self._check(f(self._s, len(px), px.ctypes.data, py.ctypes.data, k.ctypes.data, bounce.ctypes.data, out.ctypes.data),
+                    "iile_sample_table_records")
+        return out
 
     def camera_rays(self, pfilm, plens=None):
         pfilm = _f32(pfilm)

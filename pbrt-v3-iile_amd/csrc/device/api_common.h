@@ -124,6 +124,7 @@ struct iile_scene {
     iile_probe_setup probe;
     const uint32_t *probe_pixel_offsets = nullptr;
     const float *probe_filter_table = nullptr;
+    uint64_t sample_table_bytes = 0;  // HBM held by the sample table (ds.stab_*); 0: the scene has none
     uint32_t *flag_count = nullptr;  // whole-number film positions (PassBuffers::flag_count / flag_rec)
     float *flag_rec = nullptr;
     iile::DevBlock probe_block;  // cameras + aux + outputs of the last probe batch
@@ -160,6 +161,11 @@ int ensure_film(iile_scene *sc, uint32_t n_tiles, uint32_t n_pixels, uint64_t n_
 int frame_pass(iile_scene *sc, const DScene &S, int rank, int nranks, hipStream_t stream, PassDesc *P);
 // Paths of one pass under the IILE_WORKSPACE_MB budget (64 GiB unless set), at `bytes_per_path` of workspace each
 uint64_t path_budget(double bytes_per_path);
+// The byte budget of a scene's sample table (build_sample_table, api_scene.hip): a scene whose table would be larger gets none
+// and renders by the digit chains. set_sample_table_budget: the test probe's override for the scenes created next (0: the constant).
+constexpr uint64_t kSampleTableBudget = uint64_t(4) << 30;
+uint64_t sample_table_budget();
+void set_sample_table_budget(uint64_t bytes);
 // Enqueue one wavefront pass on cfg.stream.
 int run_pass(iile_scene *sc, const DScene &S, int max_depth, const PassDesc &P_in, const LaunchCfg &cfg, bool timed, bool one_stream = false);
 void copy_counters(const DCounters &c, iile_stats *st);

@@ -242,6 +242,7 @@ DScene probe_scene(const iile_scene *sc, int max_depth, float diff_scale) {
     S.filter_wide = 1;
     S.filter_table = sc->probe_filter_table;
     S.pixel_offsets = sc->probe_pixel_offsets;
+    clear_sample_table(&S);  // the frame sampler's table: the probes' sampler has other offsets and another stride
     S.base_scale0 = pr.base_scales[0], S.base_scale1 = pr.base_scales[1];
     S.base_exp0 = pr.base_exponents[0], S.base_exp1 = pr.base_exponents[1];
     S.sample_stride = pr.sample_stride;

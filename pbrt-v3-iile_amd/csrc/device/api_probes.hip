@@ -112,6 +112,25 @@ int iile_halton_samples(iile_scene *sc, int32_t n, const int32_t *px, const int3
     return IILE_OK;
 }
 
+int iile_sample_table_records(iile_scene *sc, int32_t n, const int32_t *px, const int32_t *py, const int32_t *k, const int32_t *bounce,
+                              float *out8) {
+    if (!sc || n < 0 || !px || !py || !k || !bounce || !out8) return api_fail(IILE_ERR_ARG, "iile_sample_table_records: bad argument");
+    if (!sc->ds.stab_shade) return api_fail(IILE_ERR_ARG, "iile_sample_table_records: the scene has no sample table");
+    for (int i = 0; i < n; ++i)
+        if (k[i] < 0 || uint32_t(k[i]) >= sc->ds.stab_spp || bounce[i] >= sc->ds.max_depth)
+            return api_fail(IILE_ERR_ARG, "iile_sample_table_records: sample or bounce outside the table");
+    int rc = ensure_device();
+    if (rc) return rc;
+    DevBuf<int> dx, dy, dk, db;
+    DevBuf<float> dout;
+    if ((rc = dx.put(px, n)) || (rc = dy.put(py, n)) || (rc = dk.put(k, n)) || (rc = db.put(bounce, n)) || (rc = dout.alloc(size_t(n) * 8))) return rc;
+    if (n) launch_sample_table_read(sc->ds, n, dx.p, dy.p, dk.p, db.p, dout.p, probe_cfg(sc));
+    return finish(dout, out8, size_t(n) * 8);
+}
+uint64_t iile_sample_table_budget(void) { return sample_table_budget(); }
+void iile_test_sample_table_budget(uint64_t bytes) { set_sample_table_budget(bytes); }
+uint64_t iile_sample_table_bytes(const iile_scene *sc) { return sc ? sc->sample_table_bytes : 0; }
+
 int iile_camera_rays(iile_scene *sc, int32_t n, const float *pfilm2, const float *plens2, float *o3, float *d3) {
     if (!sc || n < 0 || !pfilm2 || !o3 || !d3) return api_fail(IILE_ERR_ARG, "iile_camera_rays: bad argument");
     int rc = ensure_device();

@@ -256,9 +256,14 @@ void copy_counters(const DCounters &c, iile_stats *st) {
 }
 
 // Enqueue one wavefront pass on cfg.stream.
-int run_pass(iile_scene *sc, const DScene &S, int max_depth, const PassDesc &P_in, const LaunchCfg &cfg, bool timed, bool one_stream) {
+int run_pass(iile_scene *sc, const DScene &S_in, int max_depth, const PassDesc &P_in, const LaunchCfg &cfg, bool timed, bool one_stream) {
     PassBuffers &B = sc->pb;
     PassDesc P = P_in;
+    // The scene's sample table serves the plain frame passes: the instrumented pass, listed samples and samples past the
+    // scene's own spp keep the digit chains (a probe pass's copy of the scene arrives without the table).
+    DScene S = S_in;
+    if (cfg.count_stats || P.list_px || S.probe_mode || P.k0 < 0 || uint64_t(P.k0) + uint64_t(P.kc) > uint64_t(S.stab_spp) || max_depth > S.max_depth)
+        clear_sample_table(&S);
     // camera rays made inside the first extend / shade (see PassDesc::gen_fused) where nothing else reads queue 0
     P.gen_fused = !cfg.count_stats && !P.list_px && !S.has_infinite && !S.probe_mode && !B.nray_out && !S.env_camera;  // (camera_ray<false>)
     HIP_TRY(hipMemsetAsync(B.counts, 0, kCntWords * sizeof(uint32_t), cfg.stream));

@@ -2,7 +2,10 @@
 // the device and stream utilities, and iile_scene_create / iile_scene_destroy: one refusal pass, then one builder per table
 // of DScene. The render entry points are in api_render.hip and api_iispt.hip, the kernel-level ones in api_probes.hip.
 #include <array>
+#include <chrono>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <map>
@@ -761,7 +764,68 @@ int build_light_distribution(iile_scene *sc, const iile_scene_desc &d) {
     return IILE_OK;
 }
 
+// The Halton sampler's values for the whole frame (DScene::stab_*): a sample's index is offset(pixel mod 128) + k * stride, so
+// a frame of any size draws from 128 * 128 * spp distinct samples, and everything they depend on — permutations, bases, stride,
+// spp, maxdepth, samplepixelcenter — is fixed here. One kernel fills the table with the digit chains' own floats. No table:
+// Sobol' (its sampler is four table lookups already), maxdepth 0, a table over the budget, IILE_NO_SAMPLE_TABLE set.
+int build_sample_table(iile_scene *sc, const iile_scene_desc &d) {
+    DScene &S = sc->ds;
+    clear_sample_table(&S);
+    sc->sample_table_bytes = 0;
+    const int64_t spp = d.halton.spp;
+    if (S.sobol || S.max_depth <= 0 || spp <= 0 || S.sample_stride <= 0 || std::getenv("IILE_NO_SAMPLE_TABLE")) return IILE_OK;
+    if (5 + 7 * int64_t(S.max_depth) >= int64_t(S.n_hdims)) return IILE_OK;  // the last record's last dimension: 12 + 7 (maxdepth - 1)
+    const bool lens = S.lens_radius > 0;
+    const uint64_t per_slot = uint64_t(32) * uint64_t(S.max_depth) + (lens ? 16 : 8);
+    if (uint64_t(spp) > sample_table_budget() / (uint64_t(16384) * per_slot)) return IILE_OK;
+    const uint64_t slots = uint64_t(16384) * uint64_t(spp);  // (< 2^32: the budget is far below 2^32 slots of 40 bytes or more)
+    if (slots >= (uint64_t(1) << 32)) return IILE_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    S.stab_slots = uint32_t(slots), S.stab_spp = uint32_t(spp);
+    if (spp > 1) {
+        // slot / spp as div_magic wants it (Granlund-Montgomery, round-up form): l = ceil(log2 spp), magic = floor(2^32 (2^l - spp) / spp) + 1
+        int l = 0;
+        while ((uint64_t(1) << l) < uint64_t(spp)) ++l;
+        S.stab_spp_magic = uint32_t((((uint64_t(1) << l) - uint64_t(spp)) << 32) / uint64_t(spp) + 1);
+        S.stab_spp_shift = uint32_t(l - 1);
+    }
+    // one allocation, carved cam | lens | shade. The table only saves work: where the device has no room for it the scene does
+    // without, as it does over the budget (a 2.6 GiB table beside a nearly full card must not fail the scene)
+    float2 *cam = nullptr, *lens_part = nullptr;
+    float4 *shade = nullptr;
+    auto layout = [&](Carver c) {
+        cam = c.take<float2>(slots);
+        if (lens) lens_part = c.take<float2>(slots);
+        shade = c.take<float4>(slots * uint64_t(S.max_depth) * 2);
+        return c.used;
+    };
+    void *block = nullptr;
+    if (hipMalloc(&block, layout(Carver())) != hipSuccess) {
+        (void)hipGetLastError();  // (the failure is answered here)
+        clear_sample_table(&S);
+        return IILE_OK;
+    }
+    sc->allocs.push_back(block);
+    layout(Carver(block));
+    launch_sample_table(S, cam, lens_part, shade, LaunchCfg{sc->n_cus, nullptr, false});
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return api_fail(IILE_ERR_HIP, "sample table kernel failed");
+    S.stab_cam = cam, S.stab_lens = lens_part, S.stab_shade = shade;
+    sc->sample_table_bytes = slots * per_slot;
+    if (std::getenv("IILE_TIMING"))
+        fprintf(stderr, "iile timing: sample table of %.1f MiB built in %.3f s\n", double(sc->sample_table_bytes) / 1048576.0,
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return IILE_OK;
+}
+
 }  // namespace
+
+namespace iile {
+namespace {
+uint64_t g_table_budget_override = 0;  // iile_test_sample_table_budget
+}
+uint64_t sample_table_budget() { return g_table_budget_override ? g_table_budget_override : kSampleTableBudget; }
+void set_sample_table_budget(uint64_t bytes) { g_table_budget_override = bytes; }
+}  // namespace iile
 
 extern "C" {
 
@@ -861,9 +925,10 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
         sc->n_cus = prop.multiProcessorCount;
     set_kernel_flags(*d, sc->ds);
-    // (in this order: build_top4 reads back what build_bvh packed, the light distribution kernel reads the whole scene)
+    // (in this order: build_top4 reads back what build_bvh packed, the light distribution kernel reads the whole scene, the sample
+    //  table needs the sampler, the lens and maxdepth)
     for (auto build : {build_bvh, build_top4, build_prims, build_shapes, build_materials, build_textures, build_lights, build_halton,
-                       build_sobol, build_camera_film, build_runtime, build_light_distribution}) {
+                       build_sobol, build_camera_film, build_runtime, build_light_distribution, build_sample_table}) {
         rc = build(sc, *d);
         if (rc) {
             iile_scene_destroy(sc);

@@ -210,6 +210,28 @@ DEV void sample_dimensions_n(const DScene &S, PermPtr perms, int dim0, bool dim_
     }
 }
 
+// ---- the sample table (DScene::stab_*): slots and back ----
+// the slot of sample k of pixel (px, py): halton_index's pixel class, k fastest
+DEV uint32_t sample_slot(const DScene &S, int px, int py, uint32_t k) {
+    int pmx = px - (px / 128) * 128, pmy = py - (py / 128) * 128;  // Mod(), as halton_index
+    if (pmx < 0) pmx += 128;
+    if (pmy < 0) pmy += 128;
+    return uint32_t(pmy * 128 + pmx) * S.stab_spp + k;
+}
+// the Halton index of a slot (the per-lane chains of a wavefront the table does not serve start from it)
+DEV uint32_t slot_halton_index(const DScene &S, uint32_t slot) {
+    const uint32_t cls = S.stab_spp > 1 ? div_magic(slot, S.stab_spp_magic, S.stab_spp_shift) : slot;
+    return S.pixel_offsets[cls] + (slot - cls * S.stab_spp) * uint32_t(S.sample_stride);
+}
+// A vertex that began at dimension d0 = 5 + 7 bounce with record r[0..7] = dimensions d0 .. d0 + 7 draws its continuation at
+// d0 + off: off = 0 (nothing drawn for direct light: a specular-only vertex, no lights), 1 (SampleDiscrete's sample alone: the
+// chosen light had zero probability) or 5. Sample_f takes r[off], r[off + 1], the roulette r[off + 2].
+DEV void record_continuation(const float4 &ra, const float4 &rb, int off, float *u0, float *u1, float *ur) {
+    *u0 = off == 5 ? rb.y : (off == 1 ? ra.y : ra.x);
+    *u1 = off == 5 ? rb.z : (off == 1 ? ra.z : ra.y);
+    *ur = off == 5 ? rb.w : (off == 1 ? ra.w : ra.z);
+}
+
 // ===========================================================================
 // sampling warps (core/sampling.cpp:113-130, core/sampling.h:159-163)
 // ===========================================================================

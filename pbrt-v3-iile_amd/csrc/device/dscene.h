@@ -199,6 +199,16 @@ struct DScene {
     // halton
     int base_scale0, base_scale1, base_exp0, base_exp1, sample_stride, mult_inv0, mult_inv1;
     int sample_center;  // dimensions 0 and 1 of every sample are 0.5
+    // The frame's Halton samples, tabulated at scene creation (build_sample_table, api_scene.hip; null: the scene has no table and
+    // every kernel evaluates the digit chains). A sample's values depend on its Halton index alone, and the index on
+    // (pixel mod 128, k): a *sample slot* is class * stab_spp + k, class = (py mod 128) * 128 + (px mod 128) — k fastest, as the
+    // path ids of a pixel are consecutive in k (path_pixel), so the lanes of a camera-ray wavefront read consecutive records.
+    const float2 *stab_cam;    // [slot] dimensions 0, 1 (the film position)
+    const float2 *stab_lens;   // [slot] dimensions 3, 4 (lens_radius > 0; else null)
+    const float4 *stab_shade;  // [bounce < max_depth][slot][2] dimensions 5 + 7 bounce .. 12 + 7 bounce: all a vertex can consume
+    uint32_t stab_slots;       // 128 * 128 * stab_spp
+    uint32_t stab_spp;         // samples per pixel the table covers (k < stab_spp)
+    uint32_t stab_spp_magic, stab_spp_shift;  // slot / stab_spp by div_magic (dpath.h; stab_spp > 1)
     // sobol (iile_sobol): the frame's sampler is SobolSampler — generator matrices [n_dims][32], then vdc[32], vdc_inv[32]
     int sobol, sobol_log2res, sobol_res, sobol_dims;
     const uint32_t *sobol_mat;
@@ -212,6 +222,12 @@ struct DScene {
     int max_depth;
     float rr_threshold;
 };
+// a copy of the scene constants whose sampler, sample range or kernels are not the frame's own carries no sample table (host side)
+inline void clear_sample_table(DScene *S) {
+    S->stab_cam = S->stab_lens = nullptr;
+    S->stab_shade = nullptr;
+    S->stab_slots = S->stab_spp = S->stab_spp_magic = S->stab_spp_shift = 0;
+}
 
 // queue records -------------------------------------------------------------
 // ray:  ro = (o.xyz, bitcast pid)   rd = (d.xyz, tmax)

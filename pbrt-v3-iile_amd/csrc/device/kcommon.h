@@ -22,6 +22,8 @@ namespace iile {
 //   IILE_REFILL_IDLE_SLOW / _GEN_SLOW   the same while the wavefront's lanes go idle slowly (deep trees)
 //   IILE_SHADE_WAVES / _TEX    waves per SIMD k_shade's register allocation aims at (untextured / textured build)
 //   IILE_DIRECT_SHADE_WAVES    the same for k_direct_shade (kernels_direct.hip)
+//   IILE_SHADE_TAB_REREAD      1: the table builds of k_shade read the continuation's samples from the record again (fewer live registers, two
+//                              more loads per hit: slower, profiles/sample_table_bench_ab.txt)
 // Diagnostic builds (tools/*_stamps.py, never shipped): IILE_SHADE_STAMPS, IILE_TRAV_STAMPS, IILE_SHADOW_STAMPS, IILE_TRAV_ITERSTATS.
 #ifndef IILE_TRAV_WAVES
 #define IILE_TRAV_WAVES 6  // <= 80 VGPRs, no scratch

@@ -54,12 +54,12 @@ struct PassBuffers {
     uint32_t queue_cap;
     float4 *L;          // [n_paths] radiance so far (xyz)
     float4 *beta;       // [n_paths] throughput (xyz), w = bitcast sampler dimension
-    uint32_t *hindex;   // [n_paths] Halton index of the sample
+    uint32_t *hindex;   // [n_paths] Halton index of the sample (a pass that reads the scene's sample table: its slot there, DScene::stab_*)
     float *eta_scale;   // [n_paths] etaScale of path.cpp:81 (touched only when the scene has glass)
     float4 *ray_o[2];   // ping-pong ray queues
     float4 *ray_d[2];
     // the path's state travels with its ray from bounce 1 on (dense, in queue order) instead of being fetched by path id
-    // (scattered: 64-byte sectors for 16 + 4 bytes): ray_s = (throughput xyz, Halton index), and the ray's direction record
+    // (scattered: 64-byte sectors for 16 + 4 bytes): ray_s = (throughput xyz, Halton index or sample-table slot), and the ray's direction record
     // carries sampler dimension | specularBounce << 16 in .w where tMax (always infinite there) stood
     float4 *ray_s[2];
     float4 *hits;       // [n_paths]
@@ -143,6 +143,10 @@ void launch_shadow(const DScene &S, const PassBuffers &B, int bounce, uint32_t m
 void launch_mis(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
 // the spatial light distribution's table: 2 n + 2 floats per voxel of S.light_nv (k_light_contrib, then k_light_cdf)
 void launch_light_distributions(const DScene &S, const float *samples, float *out, const LaunchCfg &cfg);
+// the sample table (DScene::stab_*): S carries its geometry (stab_slots, stab_spp and the divider); cam / lens (may be null) /
+// shade are filled by the digit chains. launch_sample_table_read: the test probe's reader (8 floats per query)
+void launch_sample_table(const DScene &S, float2 *cam, float2 *lens, float4 *shade, const LaunchCfg &cfg);
+void launch_sample_table_read(const DScene &S, int n, const int *px, const int *py, const int *k, const int *bounce, float *out, const LaunchCfg &cfg);
 void launch_miss(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
 void launch_mis_lit(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
 void launch_film_accumulate(const DScene &S, const PassDesc &P, const PassBuffers &B, const FilmBuffers &F,

@@ -34,12 +34,24 @@ __global__ __launch_bounds__(kBlock) void k_generate(DScene S, PassDesc P, PassB
         float tmax = 0;
         if (valid) {
             // Sampler::GetCameraSample (sampler.cpp:46-52): dims 0,1 film, 2 time, 3,4 lens
-            const uint32_t idx = sample_index(S, px, py, k);
-            const float u0 = sample_dimension(S, idx, 0, px, py), u1 = sample_dimension(S, idx, 1, px, py);
-            float l0 = 0, l1 = 0;
-            if (S.lens_radius > 0) {
-                l0 = sample_dimension(S, idx, 3);
-                l1 = sample_dimension(S, idx, 4);
+            // (with a sample table — DScene::stab_cam — read from it; idx is then the sample's slot, as the table build of k_shade wants)
+            uint32_t idx;
+            float u0, u1, l0 = 0, l1 = 0;
+            if (S.stab_cam) {
+                idx = sample_slot(S, px, py, k);
+                const float2 cu = S.stab_cam[idx];
+                u0 = cu.x, u1 = cu.y;
+                if (S.lens_radius > 0) {
+                    const float2 cl = S.stab_lens[idx];
+                    l0 = cl.x, l1 = cl.y;
+                }
+            } else {
+                idx = sample_index(S, px, py, k);
+                u0 = sample_dimension(S, idx, 0, px, py), u1 = sample_dimension(S, idx, 1, px, py);
+                if (S.lens_radius > 0) {
+                    l0 = sample_dimension(S, idx, 3);
+                    l1 = sample_dimension(S, idx, 4);
+                }
             }
             if (P.probe_mode) {
                 const uint32_t probe = (pid / uint32_t(P.kc)) / (256u * uint32_t(P.probe_tiles));

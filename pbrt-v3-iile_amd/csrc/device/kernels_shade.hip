@@ -1,6 +1,7 @@
 // kernels_shade.hip — k_shade: one bounce of PathIntegrator::Li for every hit of a bounce (pipeline overview in
 // kernels.hip), and the tabulation of the spatial light distribution it samples from.
 #include <cstdlib>
+#include <type_traits>
 
 #include "kcommon.h"
 
@@ -89,6 +90,45 @@ __global__ __launch_bounds__(128) void k_light_cdf(DScene S, float *out) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// The sample table (DScene::stab_*): every Halton sample of the frame, tabulated at scene creation. A frame evaluates each
+// radical inverse once per pixel that shares the index — ~127 times at 1080p; the table holds the float the digit chains give,
+// made by those chains themselves. One thread per (slot, plane): blockIdx.y = 0 the camera part, 1 + b the record of bounce b.
+__global__ __launch_bounds__(256) void k_sample_table(DScene S, float2 *cam, float2 *lens, float4 *shade) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= S.stab_slots) return;
+    const uint32_t idx = slot_halton_index(S, slot);
+    if (blockIdx.y == 0) {
+        cam[slot] = make_float2(sample_dimension(S, idx, 0), sample_dimension(S, idx, 1));
+        if (lens) lens[slot] = make_float2(sample_dimension(S, idx, 3), sample_dimension(S, idx, 4));
+        return;
+    }
+    const int b = int(blockIdx.y) - 1, d0 = 5 + 7 * b;
+    float r[8];
+    for (int i = 0; i < 8; ++i) r[i] = sample_dimension_hi(S, S.perms, idx, d0 + i);
+    float4 *rec = shade + (size_t(b) * S.stab_slots + slot) * 2;
+    rec[0] = make_float4(r[0], r[1], r[2], r[3]);
+    rec[1] = make_float4(r[4], r[5], r[6], r[7]);
+}
+// test probe: the table's entries for sample k[i] of pixel (px[i], py[i]); bounce[i] >= 0: the eight dimensions of that bounce's
+// record, bounce[i] < 0: the camera part {u0, u1, l0, l1, 0, 0, 0, 0} (l0 = l1 = 0 without a lens part)
+__global__ void k_sample_table_read(DScene S, int n, const int *px, const int *py, const int *k, const int *bounce, float *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t slot = sample_slot(S, px[i], py[i], uint32_t(k[i]));
+    float4 a = make_float4(0, 0, 0, 0), b = make_float4(0, 0, 0, 0);
+    if (bounce[i] < 0) {
+        const float2 c = S.stab_cam[slot];
+        a.x = c.x, a.y = c.y;
+        if (S.stab_lens) a.z = S.stab_lens[slot].x, a.w = S.stab_lens[slot].y;
+    } else {
+        const float4 *rec = S.stab_shade + (size_t(bounce[i]) * S.stab_slots + slot) * 2;
+        a = rec[0], b = rec[1];
+    }
+    reinterpret_cast<float4 *>(out)[2 * size_t(i)] = a;
+    reinterpret_cast<float4 *>(out)[2 * size_t(i) + 1] = b;
+}
+
 // shade: one bounce of PathIntegrator::Li (path.cpp:81-191) for every hit of the
 // queue that extend just resolved.
 // Waves per SIMD = resident blocks per CU. The plain and the extended builds run at 4 (<= 128 VGPRs, ~10 spilled to scratch
@@ -103,17 +143,30 @@ __global__ __launch_bounds__(128) void k_light_cdf(DScene S, float *out) {
 #define IILE_SHADE_WAVES_TEX 3
 #endif
 constexpr int shade_waves(bool tex) { return tex ? IILE_SHADE_WAVES_TEX : IILE_SHADE_WAVES; }
-template <bool COUNT, bool EXT, bool TEX>
+// TAB: the scene has a sample table (DScene::stab_*; never an instrumented build, never Sobol'). A wavefront whose valid lanes all
+//   sit at dimension 5 + 7 bounce — every one unless a specular-only vertex or a roulette draw made its lanes disagree — reads its
+//   vertex's eight samples as one 32-byte record; `hidx` is then the sample slot, not the Halton index. The other wavefronts run
+//   the per-lane digit chains over the permutations in HBM: this build stages nothing in LDS and has no barrier.
+#ifndef IILE_SHADE_TAB_REREAD
+#define IILE_SHADE_TAB_REREAD 0  // 1: the continuation reads its samples from the record again instead of keeping them in registers
+#endif
+template <bool COUNT, bool EXT, bool TEX, bool TAB = false>
 __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, PassDesc P, PassBuffers B, int bounce, uint32_t plane) {
-    // digit permutations of the Halton sampler staged in LDS (dynamic shared memory)
-    extern __shared__ __attribute__((aligned(16))) uint16_t s_perms_raw[];
-    if (S.sobol) {
-        // SobolSampler: four byte-table lookups per dimension, read through the caches (DScene::sobol_bt) — nothing staged
+    static_assert(!(TAB && COUNT), "the instrumented build keeps the digit chains");
+    typename std::conditional<TAB, const uint16_t *, lds_u16 *>::type s_perms;
+    if constexpr (TAB) {
+        s_perms = S.perms;
     } else {
-        for (int i = threadIdx.x; i < S.n_perms; i += kBlock) s_perms_raw[i] = S.perms[i];
+        // digit permutations of the Halton sampler staged in LDS (dynamic shared memory)
+        extern __shared__ __attribute__((aligned(16))) uint16_t s_perms_raw[];
+        if (S.sobol) {
+            // SobolSampler: four byte-table lookups per dimension, read through the caches (DScene::sobol_bt) — nothing staged
+        } else {
+            for (int i = threadIdx.x; i < S.n_perms; i += kBlock) s_perms_raw[i] = S.perms[i];
+        }
+        __syncthreads();
+        s_perms = (lds_u16 *)s_perms_raw;
     }
-    __syncthreads();
-    lds_u16 *const s_perms = (lds_u16 *)s_perms_raw;
     const uint32_t count = B.counts[kCntShade + bounce];
     const float4 *ro = B.ray_o[bounce & 1], *rd = B.ray_d[bounce & 1];
     float4 *no = B.ray_o[(bounce + 1) & 1], *nd = B.ray_d[(bounce + 1) & 1];
@@ -173,8 +226,12 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
         //   B: next direction, throughput, Russian roulette          -> next ray
         bool surface = false;  // a hit that still scatters (bounces < maxDepth)
         bool alive = false, returned_early = false;
-        uint32_t pid = 0, hidx = 0;
+        uint32_t pid = 0, hidx = 0;  // hidx: the sample's Halton (Sobol') index; TAB: its slot in the sample table
         int dim = 0;
+        // TAB: this wavefront's vertices take their samples from the table, here their record (dimensions 5 + 7 bounce ..)
+        bool tab_wave = false;
+        float4 rec_a = make_float4(0, 0, 0, 0), rec_b = make_float4(0, 0, 0, 0);
+        auto chain_index = [&]() { return TAB ? slot_halton_index(S, hidx) : hidx; };  // what the digit chains start from
         Isect is;
         Bsdf bsdf;
         F3 beta = F3{0, 0, 0}, ray_d = F3{0, 0, 1};
@@ -195,8 +252,13 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                     fused_hidx = f2b(cpf.z);
                     float cl0 = 0, cl1 = 0;
                     if (S.lens_radius > 0) {
-                        cl0 = sample_dimension(S, s_perms, fused_hidx, 3);
-                        cl1 = sample_dimension(S, s_perms, fused_hidx, 4);
+                        if (TAB) {
+                            const float2 cl = S.stab_lens[fused_hidx];
+                            cl0 = cl.x, cl1 = cl.y;
+                        } else {
+                            cl0 = sample_dimension(S, s_perms, fused_hidx, 3);
+                            cl1 = sample_dimension(S, s_perms, fused_hidx, 4);
+                        }
                     }
                     F3 co, cd;
                     float ctm;
@@ -224,7 +286,20 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                 float u_nee[4] = {0, 0, 0, 0};
                 if (bounce < S.max_depth) {
                     const int dim_u = __builtin_amdgcn_readfirstlane(dim);
-                    sample_dimensions_n<4>(S, s_perms, dim_u + 1, __ballot(dim != dim_u) == 0, dim + 1, hidx, u_nee);
+                    const bool dim_uniform = __ballot(dim != dim_u) == 0;
+                    if (TAB) {
+                        tab_wave = dim_uniform && dim_u == 5 + 7 * bounce;
+                        if (tab_wave) {
+                            const float4 *rec = S.stab_shade + (size_t(bounce) * S.stab_slots + hidx) * 2;
+                            rec_a = rec[0];
+                            rec_b = rec[1];
+                            u_nee[0] = rec_a.y, u_nee[1] = rec_a.z, u_nee[2] = rec_a.w, u_nee[3] = rec_b.x;
+                        } else {
+                            sample_dimensions_n<4>(S, s_perms, dim_u + 1, false, dim + 1, chain_index(), u_nee);
+                        }
+                    } else {
+                        sample_dimensions_n<4>(S, s_perms, dim_u + 1, dim_uniform, dim + 1, hidx, u_nee);
+                    }
                 }
                 stamps.mark(1);
                 const int prim = int(f2b(h4.x));
@@ -273,11 +348,20 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                                 int px = 0, py = 0;
                                 uint32_t kk = 0;
                                 path_pixel(S, P, pid, &px, &py, &kk);
-                                const float u0 = sample_dimension(S, s_perms, hidx, 0, px, py), u1 = sample_dimension(S, s_perms, hidx, 1, px, py);
-                                float l0 = 0, l1 = 0;
-                                if (S.lens_radius > 0) {
-                                    l0 = sample_dimension(S, s_perms, hidx, 3);
-                                    l1 = sample_dimension(S, s_perms, hidx, 4);
+                                float u0, u1, l0 = 0, l1 = 0;
+                                if (TAB) {
+                                    const float2 cu = S.stab_cam[hidx];
+                                    u0 = cu.x, u1 = cu.y;
+                                    if (S.lens_radius > 0) {
+                                        const float2 cl = S.stab_lens[hidx];
+                                        l0 = cl.x, l1 = cl.y;
+                                    }
+                                } else {
+                                    u0 = sample_dimension(S, s_perms, hidx, 0, px, py), u1 = sample_dimension(S, s_perms, hidx, 1, px, py);
+                                    if (S.lens_radius > 0) {
+                                        l0 = sample_dimension(S, s_perms, hidx, 3);
+                                        l1 = sample_dimension(S, s_perms, hidx, 4);
+                                    }
                                 }
                                 const RayDiff rdiff =
                                     S.probe_mode ? probe_differentials(S, P.probe_cams[(pid / uint32_t(P.kc)) / (256u * uint32_t(P.probe_tiles))],
@@ -303,7 +387,11 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                         // tabulated at scene creation); a zero pdf returns before any further sample.
                         int li = 0;
                         if (EXT && S.n_lights > 1) {
-                            const float ul = sample_dimension_hi(S, s_perms, hidx, dim);
+                            float ul;
+                            if (TAB && tab_wave)
+                                ul = rec_a.x;
+                            else
+                                ul = sample_dimension_hi(S, s_perms, chain_index(), dim);
                             li = sample_light(S, is.p, ul, &light_sel_pdf);
                         }
                         if (S.n_lights > 0) ++dim;
@@ -360,10 +448,19 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
         if (P.skip_last_bounce == 2 && bounce + 1 >= S.max_depth) surface = false;  // the next vertex could add nothing: see PassDesc
         if (surface) {
             // next direction (path.cpp:133-156)
-            float u_bsdf[2];
-            {
+            float u_bsdf[2], ur_tab = 0;
+            if (TAB && tab_wave) {
+                const int off = dim - (5 + 7 * bounce);
+                if (IILE_SHADE_TAB_REREAD) {
+                    const float *rf = reinterpret_cast<const float *>(S.stab_shade + (size_t(bounce) * S.stab_slots + hidx) * 2) + off;
+                    u_bsdf[0] = rf[0], u_bsdf[1] = rf[1];
+                    if (bounce > 3) ur_tab = rf[2];
+                } else {
+                    record_continuation(rec_a, rec_b, off, &u_bsdf[0], &u_bsdf[1], &ur_tab);
+                }
+            } else {
                 const int dim_u = __builtin_amdgcn_readfirstlane(dim);
-                sample_dimensions_n<2>(S, s_perms, dim_u, __ballot(dim != dim_u) == 0, dim, hidx, u_bsdf);
+                sample_dimensions_n<2>(S, s_perms, dim_u, !TAB && __ballot(dim != dim_u) == 0, dim, chain_index(), u_bsdf);
             }
             const float u0 = u_bsdf[0], u1 = u_bsdf[1];
             dim += 2;
@@ -392,7 +489,11 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                     const float mc = max3(rr_beta.x, rr_beta.y, rr_beta.z);
                     if (mc < S.rr_threshold && bounce > 3) {
                         const float q = mx(.05f, 1 - mc);
-                        const float ur = sample_dimension_hi(S, s_perms, hidx, dim);
+                        float ur;
+                        if (TAB && tab_wave)
+                            ur = ur_tab;
+                        else
+                            ur = sample_dimension_hi(S, s_perms, chain_index(), dim);
                         ++dim;
                         if (ur < q)
                             alive = false;
@@ -441,7 +542,15 @@ void launch_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int 
     const bool tex_build = cfg.count_stats || S.textured_materials || S.probe_mode;
     const dim3 grid(grid_blocks(max_rays, cfg.n_cus, shade_waves(tex_build)));
     const size_t perm_bytes = S.sobol ? size_t(16) : (size_t(S.n_perms) * sizeof(uint16_t) + 15) & ~size_t(15);
-    if (cfg.count_stats)
+    if (S.stab_shade && !cfg.count_stats) {
+        // the scene has a sample table: the builds that read it (no permutations in LDS, no dynamic shared memory)
+        if (S.textured_materials)  // (a probe pass never carries a table)
+            hipLaunchKernelGGL((k_shade<false, true, true, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, bounce, B.queue_cap);
+        else if (S.extended_features)
+            hipLaunchKernelGGL((k_shade<false, true, false, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, bounce, B.queue_cap);
+        else
+            hipLaunchKernelGGL((k_shade<false, false, false, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, bounce, B.queue_cap);
+    } else if (cfg.count_stats)
         hipLaunchKernelGGL((k_shade<true, true, true>), grid, dim3(kBlock), perm_bytes, cfg.stream, S, P, B, bounce, B.queue_cap);
     else
         // Scenes of killeroo-simple's kind (one emitting sphere, matte / plastic only) run a build of the
@@ -453,6 +562,12 @@ void launch_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int 
             hipLaunchKernelGGL((k_shade<false, true, false>), grid, dim3(kBlock), perm_bytes, cfg.stream, S, P, B, bounce, B.queue_cap);
         else
             hipLaunchKernelGGL((k_shade<false, false, false>), grid, dim3(kBlock), perm_bytes, cfg.stream, S, P, B, bounce, B.queue_cap);
+}
+void launch_sample_table(const DScene &S, float2 *cam, float2 *lens, float4 *shade, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_sample_table, dim3((S.stab_slots + 255) / 256, 1 + S.max_depth), dim3(256), 0, cfg.stream, S, cam, lens, shade);
+}
+void launch_sample_table_read(const DScene &S, int n, const int *px, const int *py, const int *k, const int *bounce, float *out, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_sample_table_read, dim3((n + 127) / 128), dim3(128), 0, cfg.stream, S, n, px, py, k, bounce, out);
 }
 void launch_light_distributions(const DScene &S, const float *samples, float *out, const LaunchCfg &cfg) {
     const int n = S.light_nv[0] * S.light_nv[1] * S.light_nv[2];

@@ -55,12 +55,25 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_extend(DScene S
                     int px = 0, py = 0;
                     uint32_t k = 0;
                     if (path_pixel(S, P, slot, &px, &py, &k)) {  // queue 0 is dense: slot == path id
-                        const uint32_t idx = sample_index(S, px, py, k);
-                        const float u0 = sample_dimension(S, idx, 0, px, py), u1 = sample_dimension(S, idx, 1, px, py);
-                        float l0 = 0, l1 = 0;
-                        if (S.lens_radius > 0) {
-                            l0 = sample_dimension(S, idx, 3);
-                            l1 = sample_dimension(S, idx, 4);
+                        // the camera sample: from the scene's sample table where it has one (idx is then the sample's slot, which
+                        // is what the table build of k_shade wants), else by the sampler's digit chains
+                        uint32_t idx;
+                        float u0, u1, l0 = 0, l1 = 0;
+                        if (S.stab_cam) {
+                            idx = sample_slot(S, px, py, k);
+                            const float2 cu = S.stab_cam[idx];
+                            u0 = cu.x, u1 = cu.y;
+                            if (S.lens_radius > 0) {
+                                const float2 cl = S.stab_lens[idx];
+                                l0 = cl.x, l1 = cl.y;
+                            }
+                        } else {
+                            idx = sample_index(S, px, py, k);
+                            u0 = sample_dimension(S, idx, 0, px, py), u1 = sample_dimension(S, idx, 1, px, py);
+                            if (S.lens_radius > 0) {
+                                l0 = sample_dimension(S, idx, 3);
+                                l1 = sample_dimension(S, idx, 4);
+                            }
                         }
                         F3 o, d;
                         float tmax;
@@ -70,7 +83,7 @@ __global__ __launch_bounds__(kTravBlock, IILE_TRAV_WAVES) void k_extend(DScene S
                         // (no PassBuffers::hindex entry: the index rides in the record below, the film kernels work it out again)
                         // the film position rides in the path's (not yet used) throughput record: the first k_shade
                         // rebuilds the ray from it instead of evaluating the Halton dimensions again
-                        B.beta[slot] = make_float4(pfx, pfy, b2f(idx), 0.f);  // (+ the Halton index: one record, one load in k_shade)
+                        B.beta[slot] = make_float4(pfx, pfy, b2f(idx), 0.f);  // (+ the Halton index or the table slot: one record, one load in k_shade)
                         gen_d = make_float4(d.x, d.y, d.z, tmax);
                         trav_begin<COUNT>(S, t, o, d, tmax, &st, sr.root);
                         active = true;
