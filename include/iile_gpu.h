@@ -124,6 +124,17 @@ int iile_render(iile_scene *scene, const iile_render_params *params, float *film
  * otherwise; the next iile_render on the scene makes the same check on entry, so the error cannot go unseen. The reference has
  * no such state: SamplerIntegrator::Render returns when the film is complete (integrator.cpp:331-339). */
 int iile_render_status(iile_scene *scene, void *stream);
+/* SamplerIntegrator::Render with AOIntegrator::Li (src/integrators/ao.cpp:57-103; Integrator "ambientocclusion", api.cpp:1733): per
+ * camera sample one closest hit, then params->n_samples any-hit rays over the hemisphere about the geometric normal, drawn from the
+ * sampler's 2D array (Sampler::Request2DArray / Get2DArray, sampler.cpp:76-98, 136-166: entry j of pixel sample k is sample
+ * k n_samples + j of the pixel, dimensions 5 and 6); L = the sum of Dot(wi, n) / (pdf nSamples) over the unoccluded ones, in array
+ * order. Everything around Li is iile_render's: tile loop, "pixelbounds", the radiance guards, film, filter tables, exact finish, and
+ * iile_render_params is honoured as there (time_kernels brackets the film kernels only). Any scene renders, whatever integrator
+ * its file names: no material and no light is read. Counters (collect_stats): camera_rays, closest_rays, shadow_rays (the occlusion
+ * rays), nodes_closest / nodes_any, tri_tests, tri_hits, any_tri_tests, sphere_tests. Passes are sized so that their paths x
+ * n_samples rays (37 B each) fit the IILE_WORKSPACE_MB budget. IILE_ERR_ARG: n_samples < 1, sampler tables of fewer than 7
+ * dimensions; IILE_ERR_UNSUPPORTED: n_samples > 2^20, or a sample number k_end n_samples whose Halton or Sobol' index leaves 32 bits. */
+int iile_render_ao(iile_scene *scene, const iile_ao_params *params, const iile_render_params *render, float *film_xyzw, iile_stats *stats);
 /* Test probe: force the capacity (pixel hits per pass and tile sums per render) of the exact film finish for the scene's next
  * renders; 0 = sized from the frame again. */
 int iile_test_patch_capacity(iile_scene *scene, uint32_t capacity);
@@ -169,6 +180,15 @@ int iile_camera_rays(iile_scene *scene, int32_t n, const float *pfilm2, const fl
  * after the NaN / negative / inf guards; nrays (optional): {closest, shadow} per sample. */
 int iile_li_samples(iile_scene *scene, int32_t n, const int32_t *px, const int32_t *py, const int32_t *k,
                     float *L3, int32_t *nrays2);
+/* The ambient occlusion integrator's two probes. iile_ao_array_samples: out2[2i ..] = entry j[i] of the 2D array of n_samples entries
+ * for pixel sample k[i] of pixel (px[i], py[i]) — SampleDimension(GetIndexForSample(k n_samples + j), 5) and (.., 6).
+ * iile_ao_li_samples: AOIntegrator::Li of n individual camera samples through iile_render_ao's kernels, after the NaN / negative /
+ * inf guards: L1[i] (the Spectrum's one value); nrays2 (optional): {closest, occlusion} rays per sample — {1, n_samples} where the
+ * camera ray found a surface, {1, 0} where it left the scene. */
+int iile_ao_array_samples(iile_scene *scene, int32_t n_samples, int32_t n, const int32_t *px, const int32_t *py, const int32_t *k,
+                          const int32_t *j, float *out2);
+int iile_ao_li_samples(iile_scene *scene, const iile_ao_params *params, int32_t n, const int32_t *px, const int32_t *py, const int32_t *k,
+                       float *L1, int32_t *nrays2);
 /* BSDF::f / Pdf (out: 4 floats {f.rgb, pdf}) and BSDF::Sample_f (out: 7 floats
  * {wi.xyz, f.rgb, pdf}) of material `mat` in the canonical frame ns=ng=+z, ss=+x. */
 int iile_bsdf_eval(iile_scene *scene, int32_t n, int32_t mat, const float *wo3, const float *wi3, float *out4);

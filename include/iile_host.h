@@ -64,6 +64,7 @@ typedef struct iile_host_scene_info {
 } iile_host_scene_info;
 #define IILE_INTEGRATOR_PATH 0
 #define IILE_INTEGRATOR_IISPT 1
+#define IILE_INTEGRATOR_AO 2 /* Integrator "ambientocclusion" (src/core/api.cpp:1733, src/integrators/ao.cpp): iile_render_ao renders it */
 
 /* Parse a .pbrt file (plus its Includes), tessellate, build the BVH and the
  * sampler tables. Stands where ParseFile + pbrtWorldEnd's MakeScene /
@@ -74,6 +75,10 @@ const iile_scene_desc *iile_host_scene_desc(const iile_host_scene *scene);
 /* &desc->film, for bindings that do not mirror the whole iile_scene_desc. */
 const iile_film_desc *iile_host_scene_film(const iile_host_scene *scene);
 int iile_host_scene_get_info(const iile_host_scene *scene, iile_host_scene_info *info);
+/* "nsamples" / "cossample" of an Integrator "ambientocclusion" scene (CreateAOIntegrator, src/integrators/ao.cpp:105-126; nsamples is 1
+ * under quick_render), for iile_render_ao. Non-zero for a null argument or a scene of another integrator. (iile_host_scene_info keeps
+ * its 15 members.) */
+int iile_host_scene_ao(const iile_host_scene *scene, iile_ao_params *out);
 /* Film "string filename" of the scene file ("pbrt.exr" when it names none, src/core/api.cpp MakeFilm / film.cpp:262). */
 const char *iile_host_scene_film_filename(const iile_host_scene *scene);
 /* Disks and cylinders of the scene (iile_scene_desc::n_quadrics; iile_host_scene_info::n_triangles leaves them out), or -1. */

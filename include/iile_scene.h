@@ -324,6 +324,13 @@ typedef struct iile_integrator {
     int32_t pixel_bounds[4];
 } iile_integrator;
 
+/* AOIntegrator knobs (src/integrators/ao.cpp:105-126). Not part of iile_scene_desc, whose layout is closed: the host library hands
+ * them out (iile_host_scene_ao, iile_host.h) and iile_render_ao (iile_gpu.h) takes them per call. */
+typedef struct iile_ao_params {
+    int32_t n_samples;  /* "nsamples" (64; 1 under --quick): occlusion rays per camera sample, the size of the sampler's 2D array */
+    int32_t cos_sample; /* "cossample" (true): CosineSampleHemisphere, else UniformSampleHemisphere */
+} iile_ao_params;
+
 /* The IISPT probe pass: what IISPTdIntegrator::RenderView renders from a HemisphericCamera
  * (src/integrators/iispt_d.cpp:66-470, src/cameras/hemispheric.cpp:15-160): a hemi_size x hemi_size film behind a
  * Gaussian filter (radius 2, alpha 2; CreateHemisphericCamera), one Halton sample per pixel from a sampler built

@@ -92,6 +92,14 @@ class RenderParams(ctypes.Structure):
                 ("film_on_device", c_i32), ("stream", c_vp)]
 
 
+class AoParams(ctypes.Structure):
+    """iile_ao_params (include/iile_scene.h): "nsamples" and "cossample" of Integrator "ambientocclusion"."""
+    _fields_ = [("n_samples", c_i32), ("cos_sample", c_i32)]
+
+
+INTEGRATOR_PATH, INTEGRATOR_IISPT, INTEGRATOR_AO = range(3)  # iile_host_scene_info::integrator
+
+
 class IisptTask(ctypes.Structure):
     """iile_iispt_task (include/iile_scene.h): one task of the IISPT render runner."""
     _fields_ = [("x0", c_i32), ("y0", c_i32), ("x1", c_i32), ("y1", c_i32), ("tilesize", c_i32), ("counter_base", c_u32),
@@ -207,7 +215,7 @@ HOST_SYMBOLS = ["iile_host_load_pbrt", "iile_host_scene_desc", "iile_host_scene_
                 "iile_host_scene_texture", "iile_host_scene_texture_level", "iile_host_scene_filter_table",
                 "iile_host_sobol_matrices", "iile_host_sobol_vdc", "iile_host_write_exr", "iile_host_write_image",
                 "iile_host_scene_film_filename", "iile_host_scene_light", "iile_host_scene_quadric_count", "iile_host_scene_quadric",
-                "iile_host_scene_material", "iile_host_scene_camera"]
+                "iile_host_scene_material", "iile_host_scene_camera", "iile_host_scene_ao"]
 class NetWeights(ctypes.Structure):
     """iile_iispt_net_weights (include/iile_gpu.h)."""
     _fields_ = [("conv_weight", c_vp * 15), ("conv_bias", c_vp * 15), ("bn_weight", c_vp * 5), ("bn_bias", c_vp * 5),
@@ -225,6 +233,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
+               "iile_render_ao", "iile_ao_array_samples", "iile_ao_li_samples",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_sample_table_records", "iile_sample_table_budget", "iile_test_sample_table_budget", "iile_sample_table_bytes", "iile_camera_rays", "iile_li_samples",
                "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_bsdf_sample_specular", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_light_sample_at", "iile_light_pdf_at", "iile_light_le", "iile_light_choose", "iile_render_probes",
                "iile_render_probes_reference", "iile_test_probe_ref_group", "iile_reference_points",
@@ -258,6 +267,7 @@ def host_lib():
         lib.iile_host_scene_film.restype = ctypes.POINTER(FilmDesc)
         lib.iile_host_scene_film.argtypes = [c_vp]
         lib.iile_host_scene_get_info.argtypes = [c_vp, ctypes.POINTER(HostSceneInfo)]
+        lib.iile_host_scene_ao.argtypes = [c_vp, ctypes.POINTER(AoParams)]
         lib.iile_host_scene_free.argtypes = [c_vp]
         lib.iile_host_scene_free.restype = None
         lib.iile_host_scene_quadric_count.argtypes = [c_vp]
@@ -337,6 +347,9 @@ def gpu_lib():
         lib.iile_scene_destroy.argtypes = [c_vp]
         lib.iile_scene_destroy.restype = None
         lib.iile_render.argtypes = [c_vp, ctypes.POINTER(RenderParams), c_vp, ctypes.POINTER(GpuStats)]
+        lib.iile_render_ao.argtypes = [c_vp, ctypes.POINTER(AoParams), ctypes.POINTER(RenderParams), c_vp, ctypes.POINTER(GpuStats)]
+        lib.iile_ao_array_samples.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
+        lib.iile_ao_li_samples.argtypes = [c_vp, ctypes.POINTER(AoParams), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         lib.iile_trace_closest.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(GpuStats)]
         lib.iile_trace_any.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(GpuStats)]
         lib.iile_halton_samples.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]
@@ -538,6 +551,16 @@ class HostScene:
         f = self.film
         return (f.crop_y1 - f.crop_y0, f.crop_x1 - f.crop_x0)
 
+    @property
+    def ao(self):
+        """{"nsamples", "cossample"} of an Integrator "ambientocclusion" scene (iile_host_scene_ao); None for any other."""
+        if self.info["integrator"] != INTEGRATOR_AO:
+            return None
+        p = AoParams()
+        if host_lib().iile_host_scene_ao(self._h, ctypes.byref(p)) != 0:
+            raise RuntimeError(f"iile_host_scene_ao failed: {host_lib().iile_host_last_error().decode()}")
+        return {"nsamples": int(p.n_samples), "cossample": bool(p.cos_sample)}
+
     def bvh(self):
         """(flattened nodes as a BVH_NODE array, triangle vertices (n_prims, 9) in BVH order, prim_shape (n_prims,)): copies."""
         head = ctypes.cast(self.desc, ctypes.POINTER(SceneDescHead)).contents
@@ -719,6 +742,47 @@ class GpuScene:
         d = st.as_dict()
         d["sample_table_bytes"] = int(gpu_lib().iile_sample_table_bytes(self._s))  # (not a field of iile_stats: its layout is pinned)
         return film, d
+
+    def _ao_params(self, nsamples, cossample):
+        ao = self.host.ao or {"nsamples": 64, "cossample": True}  # CreateAOIntegrator's defaults for a scene of another integrator
+        return AoParams(int(ao["nsamples"] if nsamples is None else nsamples), int(bool(ao["cossample"] if cossample is None else cossample)))
+
+    def render_ao(self, nsamples=None, cossample=None, k_begin=0, k_end=0, tile_rank=0, tile_nranks=1, spp_per_pass=0, collect_stats=False,
+                  film_device_ptr=None, stream=None, want_stats=True):
+        """iile_render_ao: SamplerIntegrator::Render with AOIntegrator::Li. nsamples / cossample: None takes the scene file's
+        (HostScene.ao). Returns (film, stats) as render()."""
+        ao = self._ao_params(nsamples, cossample)
+        prm = RenderParams(int(k_begin), int(k_end), int(tile_rank), int(tile_nranks), int(spp_per_pass), int(bool(collect_stats)), 0,
+                           int(film_device_ptr is not None), c_vp(stream) if stream else None)
+        st = GpuStats()
+        if film_device_ptr is not None:
+            film, ptr = None, c_vp(int(film_device_ptr))
+        else:
+            h, w = self.host.film_shape
+            film = np.zeros((h, w, 4), np.float32)
+            ptr = film.ctypes.data
+        rc = gpu_lib().iile_render_ao(self._s, ctypes.byref(ao), ctypes.byref(prm), ptr, ctypes.byref(st) if want_stats else None)
+        self._check(rc, "iile_render_ao")
+        return film, (st.as_dict() if want_stats else None)
+
+    def ao_array_samples(self, nsamples, px, py, k, j):
+        """iile_ao_array_samples: (n, 2) float32, entry j[i] of the 2D array of `nsamples` entries for pixel sample k[i] of pixel i."""
+        px, py, k, j = _i32(px), _i32(py), _i32(k), _i32(j)
+        out = np.empty((len(px), 2), np.float32)
+        self._check(gpu_lib().iile_ao_array_samples(self._s, int(nsamples), len(px), px.ctypes.data, py.ctypes.data, k.ctypes.data, j.ctypes.data,
+                                                    out.ctypes.data), "iile_ao_array_samples")
+        return out
+
+    def ao_li_samples(self, px, py, k, nsamples=None, cossample=None):
+        """iile_ao_li_samples: (L (n,) float32 after the guards, nrays (n, 2) int32 {closest, occlusion}) of individual camera samples."""
+        ao = self._ao_params(nsamples, cossample)
+        px, py, k = _i32(px), _i32(py), _i32(k)
+        n = len(px)
+        L = np.empty(n, np.float32)
+        nr = np.empty((n, 2), np.int32)
+        self._check(gpu_lib().iile_ao_li_samples(self._s, ctypes.byref(ao), n, px.ctypes.data, py.ctypes.data, k.ctypes.data, L.ctypes.data,
+                                                 nr.ctypes.data), "iile_ao_li_samples")
+        return L, nr
 
     def render_status(self, stream=None):
         """iile_render_status: waits for `stream`; raises if the last asynchronous render's exact film finish overflowed."""

@@ -10,6 +10,8 @@
 // --iispt_hemi_size= keep the reference's spellings and defaults, src/main/pbrt.cpp:167-178). The reference starts one Python child per
 // thread for the network (IISPT_STDIO_NET_PY_PATH); here --iisptNet=FILE (or $IILE_IISPT_NET) names the weights, an IILENET1 file as
 // binding.save_net_weights writes from a checkpoint. --integrator overrides the file's line. The IISPT frame is a one-device job.
+// "ambientocclusion" -> GpuPathIntegrator too, which renders the frame through iile_render_ao (Scene::RenderFrame, csrc/host/gpu_integrator.h)
+// on one device or many; --integrator, the IISPT options and --reference are refused by name for such a scene.
 //
 // One process, the whole node (default): with several GPUs visible the frame's tiles are dealt over all of them, one host
 // thread per device, and merged by one RCCL reduction — `pbrt scene.pbrt` needs no launcher, as the reference's one Render()
@@ -226,6 +228,18 @@ int main(int argc, char **argv) {
     lap("arguments read");
     iile::Scene scene(scene_file, ps);
     lap("scene file parsed, BVH built (host)");
+    if (scene.ok() && scene.integrator() == IILE_INTEGRATOR_AO) {
+        // Integrator "ambientocclusion" is the file's choice alone: the scene was finalised for it (no bounce, no light table), and
+        // nothing of the IISPT frame or its reference mode applies to it
+        const char *flag = reference_mode ? "--reference" : (integrator_choice == IILE_INTEGRATOR_IISPT ? "--integrator iispt" :
+                           (integrator_choice == IILE_INTEGRATOR_PATH ? "--integrator path" : frame_flag));
+        if (flag) {
+            fprintf(stderr, "iile_pbrt: %s does not go with the scene file's Integrator \"ambientocclusion\"\n", flag);
+            if (comm) iile_dist_abort(comm);
+            return 1;
+        }
+        integrator_choice = IILE_INTEGRATOR_PATH;   // the same host class renders it (Scene::RenderFrame picks AOIntegrator's Li)
+    }
     if (reference_mode) {
         if (!scene.ok()) return 1;
         if (ranked && gpus_given) {

@@ -150,6 +150,7 @@ struct iile_scene {
     bool overflow_unchecked = false;     // an asynchronous render left patch.counters[2] unread
     hipStream_t overflow_stream = nullptr;
     iile::DevBlock scratch;              // device scratch of the IISPT slices (scratch_reserve)
+    iile::DevBlock ao_block;             // the occlusion rays of an ambient occlusion pass (api_ao.hip carves iile::AoBuffers from it)
 };
 
 namespace iile {
@@ -169,4 +170,17 @@ void set_sample_table_budget(uint64_t bytes);
 // Enqueue one wavefront pass on cfg.stream.
 int run_pass(iile_scene *sc, const DScene &S, int max_depth, const PassDesc &P_in, const LaunchCfg &cfg, bool timed, bool one_stream = false);
 void copy_counters(const DCounters &c, iile_stats *st);
+// What render_frame — SamplerIntegrator::Render: tile loop, pixel bounds, guards, film, exact finish — needs of the integrator whose
+// Li it renders: the workspace a camera sample of a pass takes (the IILE_WORKSPACE_MB budget sizes the passes by it), a further bound
+// on a pass's camera samples with the message of a frame whose single tile exceeds it, the integrator's own buffers for passes of
+// n_paths (may be null), and the pass itself, enqueued on cfg.stream. iile_render: run_pass; iile_render_ao: api_ao.hip.
+struct FrameIntegrator {
+    double bytes_per_path;
+    uint64_t max_pass_paths;
+    const char *too_many;
+    int (*reserve)(iile_scene *sc, uint32_t n_paths, void *ctx);
+    int (*run)(iile_scene *sc, const DScene &S, const PassDesc &P, const LaunchCfg &cfg, bool timed, bool one_stream, void *ctx);
+    void *ctx;
+};
+int render_frame(iile_scene *sc, const iile_render_params *prm, float *film_xyzw, iile_stats *stats, const FrameIntegrator &fi);
 }  // namespace iile

@@ -1,5 +1,6 @@
 // api_render.hip — the path integrator's half of the C ABI (include/iile_gpu.h): the wavefront workspace and the film
-// blocks, the set-up of a frame's passes, run_pass (the schedule of the kernels in kernels*.hip), iile_render,
+// blocks, the set-up of a frame's passes, run_pass (the schedule of the kernels in kernels*.hip), render_frame
+// (SamplerIntegrator::Render around an integrator's pass: iile_render here, iile_render_ao in api_ao.hip), iile_render,
 // iile_render_status and iile_li_samples.
 #include <chrono>
 #include <cmath>
@@ -336,14 +337,11 @@ int run_pass(iile_scene *sc, const DScene &S_in, int max_depth, const PassDesc &
     HIP_TRY(hipGetLastError());
     return IILE_OK;
 }
-}  // namespace iile
 
-extern "C" {
-int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw, iile_stats *stats) {
-    if (!sc || !prm || !film_xyzw) return api_fail(IILE_ERR_ARG, "iile_render: null argument");
-    int rc = ensure_device();
-    if (rc) return rc;
-    rc = check_pending_overflow(sc);   // of an earlier render that returned before its stream had drained
+// SamplerIntegrator::Render (integrator.cpp:227-331) around the Li of `fi`: the tile loop over the rank's share, pixel bounds,
+// radiance guards, the film with its filter tables and the exact finish. iile_render and iile_render_ao are this with their own pass.
+int render_frame(iile_scene *sc, const iile_render_params *prm, float *film_xyzw, iile_stats *stats, const FrameIntegrator &fi) {
+    int rc = check_pending_overflow(sc);   // of an earlier render that returned before its stream had drained
     if (rc) return rc;
     const DScene &S = sc->ds;
     int k_begin = prm->k_begin, k_end = prm->k_end;
@@ -370,16 +368,18 @@ int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw,
     // A pass renders all samples of a range of owned tiles; the range is bounded by the workspace budget (~410 B per
     // path incl. queue padding). `spp_per_pass` (tests) asks for passes of about that many samples per pixel's worth
     // of paths: n_owned_tiles * spp_per_pass / n_samples tiles each.
-    uint64_t max_paths = path_budget(410.0);
+    uint64_t max_paths = std::min<uint64_t>(path_budget(fi.bytes_per_path), fi.max_pass_paths);
     if (prm->spp_per_pass > 0) max_paths = std::min<uint64_t>(max_paths, std::max<uint64_t>(1, pix_slots * uint64_t(prm->spp_per_pass)));
     const uint64_t paths_per_tile = uint64_t(256) * uint64_t(n_samples);
     if (paths_per_tile > kMaxPassPaths) return api_fail(IILE_ERR_UNSUPPORTED, "more than 781 250 samples per pixel in one render: split the sample range");
+    if (paths_per_tile > fi.max_pass_paths) return api_fail(IILE_ERR_UNSUPPORTED, fi.too_many);
     const int tiles_per_pass = int(std::max<uint64_t>(1, std::min<uint64_t>(uint64_t(std::max(P.n_owned_tiles, 1)), max_paths / paths_per_tile)));
     const uint32_t fw = uint32_t(S.crop_x1 - S.crop_x0), fh = uint32_t(S.crop_y1 - S.crop_y0);
 
     if (pix_slots) {
         rc = ensure_workspace(sc, uint32_t(uint64_t(tiles_per_pass) * paths_per_tile));
         if (rc) return rc;
+        if (fi.reserve && (rc = fi.reserve(sc, uint32_t(uint64_t(tiles_per_pass) * paths_per_tile), fi.ctx))) return rc;
     }
     rc = ensure_film(sc, uint32_t(P.n_owned_tiles), fw * fh, S.filter_wide ? pix_slots * uint64_t(n_samples) : 0);
     if (rc) return rc;
@@ -415,7 +415,7 @@ int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw,
         P.n_pass_tiles = std::min(tiles_per_pass, P.n_owned_tiles - slot0);
         P.n_paths = uint32_t(uint64_t(P.n_pass_tiles) * paths_per_tile);
         if (sc->pb.flag_count) HIP_TRY(hipMemsetAsync(sc->flag_count, 0, sizeof(uint32_t), stream));
-        rc = run_pass(sc, S, sc->max_depth, P, cfg, timed, prm->time_kernels == 2);
+        rc = fi.run(sc, S, P, cfg, timed, prm->time_kernels == 2, fi.ctx);
         if (rc) return rc;
         rc = timed_step(sc, timed, stream, 4, [&] {
             if (S.filter_wide)
@@ -495,6 +495,21 @@ int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw,
         if (stats) *stats = st;
     }
     return IILE_OK;
+}
+}  // namespace iile
+
+extern "C" {
+int iile_render(iile_scene *sc, const iile_render_params *prm, float *film_xyzw, iile_stats *stats) {
+    if (!sc || !prm || !film_xyzw) return api_fail(IILE_ERR_ARG, "iile_render: null argument");
+    const int rc = ensure_device();
+    if (rc) return rc;
+    // PathIntegrator::Li: ~410 B of workspace per path incl. queue padding
+    static const FrameIntegrator path = {410.0, kMaxPassPaths, "", nullptr,
+                                         [](iile_scene *s, const DScene &S, const PassDesc &P, const LaunchCfg &cfg, bool timed, bool one_stream, void *) {
+                                             return run_pass(s, S, s->max_depth, P, cfg, timed, one_stream);
+                                         },
+                                         nullptr};
+    return render_frame(sc, prm, film_xyzw, stats, path);
 }
 int iile_render_status(iile_scene *sc, void *stream) {
     if (!sc) return api_fail(IILE_ERR_ARG, "iile_render_status: null scene");

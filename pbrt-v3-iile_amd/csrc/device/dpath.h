@@ -196,6 +196,30 @@ DEV float sample_dimension_hi(const DScene &S, PermPtr perms, uint32_t index, in
 DEV float sample_dimension(const DScene &S, uint32_t index, int dim, int px = 0, int py = 0) {
     return sample_dimension(S, S.perms, index, dim, px, py);
 }
+// ---- array samples (Sampler::Request2DArray / Get2DArray, core/sampler.cpp:76-98; GlobalSampler::StartPixel, :136-166) ----
+// A GlobalSampler fills a requested 2D array of n entries per pixel sample from the samples k n .. k n + n - 1 of the pixel:
+// entry j of pixel sample k is {SampleDimension(GetIndexForSample(k n + j), dim), SampleDimension(.., dim + 1)}. Arrays start at
+// arrayStartDim = 5, behind the camera sample's dimensions 0 .. 4, the 1D arrays first, then the 2D ones two dimensions each:
+// `dim` is the array's own first dimension (5 for an integrator's only array). The sample number k n + j runs past the scene's
+// pixelsamples, so this goes by the sampler's index and radical-inverse code, never by the sample table.
+// (Not built: arrayEndDim, by which the ordinary dimensions of Get1D / Get2D step over the arrays, sampler.cpp:180-195 — nothing
+//  here draws after an array yet. A caller that does adds the arrays' dimensions to its own counter.)
+DEV void sample_array_2d(const DScene &S, int px, int py, uint32_t k, uint32_t n, uint32_t j, int dim, float *u0, float *u1) {
+    const uint32_t idx = sample_index(S, px, py, k * n + j);
+    *u0 = sample_dimension(S, idx, dim, px, py);
+    *u1 = sample_dimension(S, idx, dim + 1, px, py);
+}
+
+// core/sampling.cpp:89-96
+DEV F3 uniform_sample_hemisphere(float u0, float u1) {
+    const float z = u0;
+    const float r = sqrtf(mx(0.f, 1.f - z * z));
+    const float phi = 2 * kPi * u1;
+    float s, c;
+    sincos_f(phi, &s, &c);
+    return F3{r * c, r * s, z};
+}
+
 // N consecutive dimensions >= 2 of one sample (the shade kernel's batches)
 template <int N, typename PermPtr>
 DEV void sample_dimensions_n(const DScene &S, PermPtr perms, int dim0, bool dim_uniform, int dim_lane, uint32_t index, float *out) {

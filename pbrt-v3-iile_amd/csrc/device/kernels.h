@@ -172,6 +172,23 @@ void launch_probe_finish(const DScene &S, const PassDesc &P, const PassBuffers &
                          float *intensity, float *normals, float *distance, const LaunchCfg &cfg);
 void launch_film_resolve(const DScene &S, const PassDesc &P, const FilmBuffers &F, const LaunchCfg &cfg);
 
+// ---- the ambient occlusion integrator (kernels_ao.hip; AOIntegrator::Li, src/integrators/ao.cpp:57-103) ----
+// A pass's occlusion rays, path-major: the n_samples rays of hit h (the h-th camera ray k_ao_rays found a surface for, in whatever
+// order its wavefronts came) are h * n_samples + j, j the entry of the sampler's 2D array.
+struct AoBuffers {
+    float4 *ray_o, *ray_d;   // [max_rays] isect.SpawnRay(wi): (origin, 0), (wi, tMax = inf)
+    float *term;             // [max_rays] Dot(wi, n) / (pdf * nSamples): what the ray adds to L when nothing occludes it
+    uint8_t *vis;            // [max_rays] k_ao_occlude: 1 = unoccluded
+    uint32_t *hit_pid;       // [n_paths] the path (camera sample) of hit h
+    int n_samples, cos_sample;
+};
+// counts words of a pass of the AO integrator (it has no NEE records: their words are free): hits so far, the ray feed's cursor
+constexpr int kCntAoHits = 16, kCntAoHead = 64;
+void launch_ao_rays(const DScene &S, const PassDesc &P, const PassBuffers &B, const AoBuffers &A, const LaunchCfg &cfg);
+void launch_ao_occlude(const DScene &S, const PassBuffers &B, const AoBuffers &A, uint32_t max_rays, const LaunchCfg &cfg);
+void launch_ao_fold(const PassDesc &P, const PassBuffers &B, const AoBuffers &A, const LaunchCfg &cfg);
+void launch_ao_array_probe(const DScene &S, int n_samples, int n, const int *px, const int *py, const int *k, const int *j, float *out2, const LaunchCfg &cfg);
+
 // ---- the IISPT runner's gather (iispt.hip) ----
 struct DHemiCam {  // a hemi point's HemisphericCamera as the gather uses it (cameras/hemispheric.h:23-82)
     M44 c2w;       // CameraToWorld

@@ -90,6 +90,13 @@ bool finalize_scene(HostScene *s, std::string *err) {
         return false;
     }
     build_bvh(s);
+    if (s->integrator_ao) {
+        // AOIntegrator::Li follows no path (ao.cpp:57-103): one camera ray, then the any-hit rays of its 2D sample array, which takes
+        // dimensions 5 and 6 (the camera sample keeps 0 .. 4) — build_halton_tables covers 64 at least. No bounce means no sample
+        // table, and it reads no light: no spatial light distribution is built for it either.
+        s->max_depth = 0;
+        s->light_strategy = "uniform";
+    }
     build_halton_tables(s);
     if (s->sampler_name == "sobol") {
         // GlobalSampler(RoundUpPow2(samplesPerPixel)), samplers/sobol.h:59-64 — before anything reads the sample count

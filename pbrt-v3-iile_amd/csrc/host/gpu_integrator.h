@@ -67,6 +67,13 @@ class Scene {
         return host_ && iile_host_scene_get_info(host_, &info) == 0 ? info.integrator : IILE_INTEGRATOR_PATH;
     }
     std::string film_filename() const { return host_ ? iile_host_scene_film_filename(host_) : std::string(); }
+    // Integrator "ambientocclusion": its "nsamples" / "cossample" (CreateAOIntegrator, ao.cpp:122-124); false for any other scene
+    bool ao(iile_ao_params *out) const { return host_ && integrator() == IILE_INTEGRATOR_AO && iile_host_scene_ao(host_, out) == 0; }
+    // SamplerIntegrator::Render with the Li of the scene file's integrator: AOIntegrator's for "ambientocclusion", else PathIntegrator's
+    int RenderFrame(iile_scene *gpu, const iile_render_params *prm, float *film_xyzw, iile_stats *st) const {
+        iile_ao_params ao_params;
+        return ao(&ao_params) ? iile_render_ao(gpu, &ao_params, prm, film_xyzw, st) : iile_render(gpu, prm, film_xyzw, st);
+    }
 
   private:
     iile_host_scene *host_ = nullptr;
@@ -112,7 +119,7 @@ class GpuPathIntegrator : public Integrator {
         prm.tile_nranks = nranks_;
         prm.collect_stats = stats_ ? 1 : 0;
         iile_stats st;
-        const int rc = iile_render(gpu, &prm, xyzw.data(), &st);
+        const int rc = scene.RenderFrame(gpu, &prm, xyzw.data(), &st);
         iile_scene_destroy(gpu);
         if (rc != IILE_OK) {
             fprintf(stderr, "Error: GPU path: %s\n", iile_last_error());
@@ -238,7 +245,7 @@ class GpuPathIntegrator : public Integrator {
             prm.tile_nranks = nranks_;
             prm.collect_stats = stats_ ? 1 : 0;
             prm.film_on_device = 1;
-            if (iile_render(gpu, &prm, static_cast<float *>(film_dev), &st) != IILE_OK) {
+            if (scene.RenderFrame(gpu, &prm, static_cast<float *>(film_dev), &st) != IILE_OK) {
                 fprintf(stderr, "Error: GPU path: %s\n", iile_last_error());
                 ok = false;
             }

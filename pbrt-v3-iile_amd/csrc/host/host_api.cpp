@@ -39,6 +39,7 @@ int iile_host_load_pbrt(const char *path, const iile_host_overrides *ov, iile_ho
                 hs->s.xres = std::max(1, hs->s.xres / 4);
                 hs->s.yres = std::max(1, hs->s.yres / 4);
                 hs->s.spp = 1;
+                hs->s.ao_nsamples = 1;   // `if (PbrtOptions.quickRender) nSamples = 1;`, ao.cpp:124
                 // Light::nSamples of area and infinite lights: max(1, nSamples / 4) (diffuse.cpp:143, infinite.cpp:183)
                 for (iile_light &lt : hs->s.lights)
                     if (lt.n_samples > 1) lt.n_samples = std::max(1, lt.n_samples / 4);
@@ -115,7 +116,21 @@ int iile_host_scene_get_info(const iile_host_scene *scene, iile_host_scene_info 
     info->spp = s.spp;
     info->max_depth = s.max_depth;
     info->probe_hemi_size = s.desc.probe.hemi_size;
-    info->integrator = s.integrator_iispt ? IILE_INTEGRATOR_IISPT : IILE_INTEGRATOR_PATH;
+    info->integrator = s.integrator_ao ? IILE_INTEGRATOR_AO : (s.integrator_iispt ? IILE_INTEGRATOR_IISPT : IILE_INTEGRATOR_PATH);
+    return 0;
+}
+
+int iile_host_scene_ao(const iile_host_scene *scene, iile_ao_params *out) {
+    if (!scene || !out) {
+        g_err = "iile_host_scene_ao: null argument";
+        return 1;
+    }
+    if (!scene->s.integrator_ao) {
+        g_err = "iile_host_scene_ao: the scene's Integrator is not \"ambientocclusion\"";
+        return 2;
+    }
+    out->n_samples = scene->s.ao_nsamples;
+    out->cos_sample = scene->s.ao_cossample ? 1 : 0;
     return 0;
 }
 

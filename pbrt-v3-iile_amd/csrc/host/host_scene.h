@@ -60,6 +60,9 @@ struct HostScene {
     std::string integrator_name = "path";
     int max_depth = 5;
     bool integrator_iispt = false;   // Integrator "iispt" (MakeIntegrator, src/core/api.cpp:1738-1760)
+    bool integrator_ao = false;      // Integrator "ambientocclusion" (api.cpp:1733): "nsamples", "cossample" (ao.cpp:122-124)
+    int ao_nsamples = 64;
+    bool ao_cossample = true;
     float rr_threshold = 1.f;
     bool has_pixel_bounds = false;   // "pixelbounds" of the path integrator: x0, x1, y0, y1 as given (path.cpp:216-229)
     int pixel_bounds_given[4] = {0, 0, 0, 0};

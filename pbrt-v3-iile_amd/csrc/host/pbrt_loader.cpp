@@ -480,8 +480,17 @@ class Loader {
         } else if (d == "Integrator") {  // integrators/path.cpp:214-231
             // "iispt" (CreateIISPTIntegrator, src/integrators/iispt.cpp:790-820) reads the same parameters; which of the two renders
             // the frame is the host's choice (iile_host_scene_info::integrator)
-            if (name != "path" && name != "iispt") return fail("only Integrator \"path\" and \"iispt\" are supported, got " + name);
+            // "ambientocclusion" (CreateAOIntegrator, src/integrators/ao.cpp:105-126) reads "pixelbounds" as the path integrator does,
+            // "cossample" and "nsamples"; RoundCount is the identity for both samplers here (sampler.h:72), so nsamples stands as given
+            if (name != "path" && name != "iispt" && name != "ambientocclusion")
+                return fail("only Integrator \"path\" and \"iispt\" and \"ambientocclusion\" are supported, got " + name);
             s.integrator_iispt = name == "iispt";
+            s.integrator_ao = name == "ambientocclusion";
+            if (s.integrator_ao) {
+                s.ao_cossample = ps.one_bool("cossample", true);
+                s.ao_nsamples = ps.one_int("nsamples", 64);
+                if (s.ao_nsamples < 1) return fail("Integrator \"ambientocclusion\": \"nsamples\" must be at least 1, got " + std::to_string(s.ao_nsamples));
+            }
             s.max_depth = ps.one_int("maxdepth", 5);
             s.rr_threshold = ps.one_float("rrthreshold", 1.);
             s.light_strategy = ps.one_string("lightsamplestrategy", "spatial");
