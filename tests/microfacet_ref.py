@@ -89,10 +89,10 @@ def tr_pdf(wo, wh, ax, ay):
     return tr_d(wh, ax, ay) * tr_g1(wo, ax, ay) * np.abs(_dot(wo, wh)) / np.abs(wo[:, 2])
 
 
-def _sample11(cos_theta, u1, u2):
-    """TrowbridgeReitzSample11, microfacet.cpp:238-283."""
+def _sample11(cos_theta, u1, u2, dtype=np.float64):
+    """TrowbridgeReitzSample11, microfacet.cpp:238-283; every operation in `dtype`."""
     n = len(cos_theta)
-    sx, sy = np.empty(n), np.empty(n)
+    sx, sy = np.empty(n, dtype), np.empty(n, dtype)
     normal = cos_theta > .9999
     r = np.sqrt(u1[normal] / (1 - u1[normal]))
     phi = 6.28318530718 * u2[normal]
@@ -109,19 +109,20 @@ def _sample11(cos_theta, u1, u2):
     D = np.sqrt(np.maximum(B * B * tmp * tmp - (A * A - B * B) * tmp, 0))
     s1, s2 = B * tmp - D, B * tmp + D
     x = np.where((A < 0) | (s2 > 1 / tan_t), s1, s2)
-    S = np.where(U2 > 0.5, 1.0, -1.0)
+    S = np.where(U2 > 0.5, 1.0, -1.0).astype(dtype)
     U2 = np.where(U2 > 0.5, 2 * (U2 - .5), 2 * (.5 - U2))
     z = (U2 * (U2 * (U2 * 0.27385 - 0.73369) + 0.46341)) / (U2 * (U2 * (U2 * 0.093073 + 0.309420) - 1.000000) + 0.597999)
     sx[o], sy[o] = x, S * z * np.sqrt(1 + x * x)
     return sx, sy
 
 
-def tr_sample_wh(wo, u0, u1, ax, ay):
-    """TrowbridgeReitzDistribution::Sample_wh, visible area (microfacet.cpp:285-336)."""
+def tr_sample_wh(wo, u0, u1, ax, ay, dtype=np.float64):
+    """TrowbridgeReitzDistribution::Sample_wh, visible area (microfacet.cpp:285-336); dtype: float64, or the arithmetic of a wo, ax,
+    ay given in another."""
     flip = wo[:, 2] < 0
     wi = np.where(flip[:, None], -wo, wo)
     ws = _normalize(np.stack([ax * wi[:, 0], ay * wi[:, 1], wi[:, 2]], 1))
-    sx, sy = _sample11(ws[:, 2], np.asarray(u0, np.float64), np.asarray(u1, np.float64))
+    sx, sy = _sample11(ws[:, 2], np.asarray(u0, dtype), np.asarray(u1, dtype), dtype)
     _, _, cp, sp = _trig(ws)
     sx, sy = cp * sx - sp * sy, sp * sx + cp * sy
     wh = _normalize(np.stack([-ax * sx, -ay * sy, np.ones_like(sx)], 1))

@@ -12,9 +12,9 @@ ETA = 1.5
 LOBES = ("lam_r", "lam_t", "micro_r", "micro_t")  # BxDF order (translucent.cpp:62-78)
 
 
-def fr_dielectric(cos_i, eta_i, eta_t):
-    """FrDielectric, reflection.cpp:47-68, elementwise over (n,) cosines."""
-    c = np.clip(np.asarray(cos_i, np.float64), -1, 1)
+def fr_dielectric(cos_i, eta_i, eta_t, dtype=np.float64):
+    """FrDielectric, reflection.cpp:47-68, elementwise over (n,) cosines; dtype: float64, or the arithmetic of etas given in another."""
+    c = np.clip(np.asarray(cos_i, dtype), -1, 1)
     entering = c > 0
     ei, et = np.where(entering, eta_i, eta_t), np.where(entering, eta_t, eta_i)
     c = np.abs(c)
