@@ -141,7 +141,7 @@ struct iile_scene {
     std::vector<int> tile_of_slot, slot_of_tile;
     iile::DevBlock tile_tables;     // tile_of_slot, then slot_of_tile
     int map_key[4] = {0, 0, 0, 0};  // {n_tiles_x, n_tiles_y, rank, nranks} the tables were built for
-    // the exact film finish on the device (kernels.hip): hit / entry records and the hash table, allocated at the first render
+    // the exact film finish on the device (kernels_film.hip): hit / entry records and the hash table, allocated at the first render
     iile::PatchDev patch{};
     iile::DevBlock patch_block;
     iile::DevBlock film_add_block;       // iile_iispt_film_add's task table (rectangles, first pixels)

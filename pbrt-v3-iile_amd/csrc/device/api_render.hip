@@ -84,7 +84,7 @@ int ensure_tile_map(iile_scene *sc, PassDesc *P, hipStream_t stream) {
     return IILE_OK;
 }
 
-// Room for the exact film finish (kernels.hip), sized from the frame: a flagged camera sample reaches at most three more
+// Room for the exact film finish (kernels_film.hip), sized from the frame: a flagged camera sample reaches at most three more
 // pixels (hits), every hit becomes at most one tile sum (entries, kept for the whole render). paths_per_pass / samples_in_render
 // bound the flagged samples of a pass / of the render; the flagged list itself holds kMaxFlagged records per pass.
 int ensure_patch(iile_scene *sc, uint64_t paths_per_pass, uint64_t samples_in_render) {
@@ -388,7 +388,7 @@ int render_frame(iile_scene *sc, const iile_render_params *prm, float *film_xyzw
     iile_stats st;
     std::memset(&st, 0, sizeof(st));
     // whole-number film positions are listed for the one-pixel box film (the sample store of wider filters handles them).
-    // Their exact finish runs on the device, on this stream, without a host wait (kernels.hip "exact film finish").
+    // Their exact finish runs on the device, on this stream, without a host wait (kernels_film.hip "exact film finish").
     if (!S.filter_wide) {
         rc = ensure_patch(sc, uint64_t(tiles_per_pass) * paths_per_tile, uint64_t(P.n_owned_tiles) * paths_per_tile);
         if (rc) return rc;

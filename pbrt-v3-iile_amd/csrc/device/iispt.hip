@@ -11,7 +11,7 @@
 //                    estimate_direct (:16-140) over the four neighbouring hemispheres the network predicted (read where
 //                    the network left them in HBM), f_beta * L
 // The host (launch_iispt_first_hits below, for api_iispt.hip) repeats trace + vertex until no item is left on a specular chain (at most 24 times, as the
-// reference's loop). Each kernel is one thread per item and about the size of the kernel-level probes of kernels.hip:
+// reference's loop). Each kernel is one thread per item and about the size of the kernel-level probes of kernels_probes.hip:
 // a first version that ran the whole loop, traversal included, inside one kernel (245 VGPRs, 170-200 spilled SGPRs)
 // produced kernels that read outside their buffers or returned garbage for glossy hits depending on the optimisation
 // level and on the heap layout of the process. This pass costs two orders of magnitude less than the probe pass and

@@ -1,7 +1,7 @@
 // kcommon.h — what the kernel translation units share: block geometry, wavefront-aggregated queue appends, the
 // persistent work feed, the layout of the per-pass counters, path -> pixel enumeration.
 // (kernels_trav.hip: extend / shadow / MIS / trace; kernels_shade.hip: shade, light distributions;
-//  kernels.hip: generation, film, probes and the remaining launchers; iispt.hip: the IISPT runner's gather.)
+//  kernels.hip: generation, miss, mis_lit; kernels_film.hip over dfilm.h: the film; kernels_probes.hip: test probes; iispt.hip: the IISPT runner's gather.)
 #pragma once
 #include <algorithm>
 

@@ -20,7 +20,7 @@
 // SpecularReflection and a SpecularTransmission lobe (glass.cpp:62-90) and both recursions fire —: scenes with glass do not take
 // this wavefront but k_direct_tree below, one thread per pixel walking the tree depth first (round 3 rendered glass black beyond
 // its direct light, which the round-3 advisor showed to be wrong).
-#include "kcommon.h"
+#include "dfilm.h"  // direct_film_add: the render loop's guards and the add into the double film, for k_direct_fold and k_direct_tree
 
 namespace iile {
 
@@ -292,7 +292,6 @@ __global__ __launch_bounds__(kBlock) void k_direct_miss(DScene S, PassBuffers B,
 // Li folded from the deepest vertex back (the recursion returns in that order), the render loop's guards
 // (directprogressiveintegrator.cpp:104-127), IisptFilmMonitor::add_n_samples (iisptfilmmonitor.cpp:47-72: doubles)
 __global__ __launch_bounds__(kBlock) void k_direct_fold(DScene S, PassDesc P, PassBuffers B, double *film_rgbw) {
-    const int fw = S.crop_x1 - S.crop_x0;
     // one thread per pixel slot; the launch's passes of that pixel are added to the film monitor one after the other, in pass
     // order (add_n_samples runs once per pass in the reference: the order of the double additions is part of the result)
     const uint32_t kc = uint32_t(P.kc);
@@ -329,19 +328,7 @@ __global__ __launch_bounds__(kBlock) void k_direct_fold(DScene S, PassDesc P, Pa
             }
             Lnext = L;
         }
-        F3 L = Lnext;
-        const float y = lum_y(L);
-        if (is_nan(L.x) || is_nan(L.y) || is_nan(L.z))
-            L = F3{0, 0, 0};
-        else if (double(y) < -1e-5)
-            L = F3{0, 0, 0};
-        else if (is_inf(y))
-            L = F3{0, 0, 0};
-        double *out = film_rgbw + 4 * (size_t(py - S.crop_y0) * fw + (px - S.crop_x0));
-        out[0] += double(L.x);
-        out[1] += double(L.y);
-        out[2] += double(L.z);
-        out[3] += 1.0;
+        direct_film_add(film_rgbw, S, px, py, Lnext);
     }
 }
 
@@ -427,7 +414,6 @@ __global__ __launch_bounds__(kBlock, 1) void k_direct_tree(DScene S, PassDesc P,
     lds_int *my_stack = (lds_int *)&lds_stack[threadIdx.x >> 6][0][threadIdx.x & 63];
     const uint32_t spill_stride = gridDim.x * kBlock;
     int *my_spill = B.spill + blockIdx.x * kBlock + threadIdx.x;
-    const int fw = S.crop_x1 - S.crop_x0;
     for (uint32_t pid = blockIdx.x * kBlock + threadIdx.x; pid < P.n_paths; pid += gridDim.x * kBlock) {
         int px = 0, py = 0;
         uint32_t kk = 0;
@@ -671,19 +657,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_direct_tree(DScene S, PassDesc P,
                 if (depth < 0) break;
             }
         }
-        F3 L = ret;
-        const float y = lum_y(L);
-        if (is_nan(L.x) || is_nan(L.y) || is_nan(L.z))
-            L = F3{0, 0, 0};
-        else if (double(y) < -1e-5)
-            L = F3{0, 0, 0};
-        else if (is_inf(y))
-            L = F3{0, 0, 0};
-        double *out = film_rgbw + 4 * (size_t(py - S.crop_y0) * fw + (px - S.crop_x0));
-        out[0] += double(L.x);
-        out[1] += double(L.y);
-        out[2] += double(L.z);
-        out[3] += 1.0;
+        direct_film_add(film_rgbw, S, px, py, ret);
     }
 }
 
