@@ -79,9 +79,11 @@ typedef struct iile_quadric {
     int32_t swaps_handedness;
 } iile_quadric;
 
-/* 7 is not a material type: a descriptor that names it is refused (IILE_ERR_UNSUPPORTED), and stays refused */
+/* 7 and 9 are not material types: a descriptor that names either is refused (IILE_ERR_UNSUPPORTED), and stays refused (callers of
+ * the ABI as it was before the Disney material hand over descriptors that end before iile_scene_desc::disney, and for them 9 was
+ * "the next unused value": it must never make this library read that member) */
 enum { IILE_MAT_MATTE = 0, IILE_MAT_PLASTIC = 1, IILE_MAT_UBER = 2, IILE_MAT_MIRROR = 3, IILE_MAT_GLASS = 4, IILE_MAT_METAL = 5,
-       IILE_MAT_SUBSTRATE = 6, IILE_MAT_TRANSLUCENT = 8 };
+       IILE_MAT_SUBSTRATE = 6, IILE_MAT_TRANSLUCENT = 8, IILE_MAT_DISNEY = 10 };
 
 /* MatteMaterial / PlasticMaterial / UberMaterial / MirrorMaterial / GlassMaterial / MetalMaterial / SubstrateMaterial /
  * TranslucentMaterial with constant textures (src/materials/matte.cpp:45-62, plastic.cpp:45-70, uber.cpp:45-100, mirror.cpp:44-55,
@@ -133,9 +135,23 @@ typedef struct iile_material {
      * Substrate (substrate.cpp:45-79): FresnelBlend(Kd, Ks) over "uroughness" / "vroughness" in the same fields as metal.
      * Translucent (translucent.cpp:45-98) adds no field: "Kd" is kd / kd_tex, "Ks" ks / ks_tex, "reflect" kr / kr_tex, "transmit"
      * kt / kt_tex, the isotropic "roughness" roughness / alpha / rough_tex (alpha_v = alpha, rough_tex_v -2), "remaproughness"
-     * remap_roughness, "bumpmap" bump_tex, and eta is 1.5; opacity is 1 and cond_eta / cond_k are 0 */
+     * remap_roughness, "bumpmap" bump_tex, and eta is 1.5; opacity is 1 and cond_eta / cond_k are 0.
+     * Disney (disney.cpp:475-624) adds no field here either: "color" is kd / kd_tex, "roughness" roughness / alpha / rough_tex with
+     * remap_roughness = 0 (the hit sees the raw roughness: Disney never remaps; alpha_v = alpha, rough_tex_v -2), "eta" eta (default
+     * 1.5), "bumpmap" bump_tex; opacity is 1 and everything else 0 / -1. Its scalar parameters are iile_scene_desc::disney[index]. */
     float cond_eta[3], cond_k[3];
 } iile_material;
+
+/* The scalar parameters of a DisneyMaterial (disney.cpp:590-624), one entry per material of the scene (zeros for a material of
+ * another type): constants, as the loader refuses a non-constant texture on any of them. "scatterdistance" has no field: only black
+ * is taken (the BSSRDF branch, disney.cpp:521-527, is not rendered). The lobes, in the order BSDF::Sample_f counts them:
+ * DisneyDiffuse, DisneyFakeSS (thin), DisneyRetro, DisneySheen (sheen > 0) — these four iff (1 - metallic)(1 - spec_trans) > 0 —
+ * MicrofacetReflection, DisneyClearcoat (clearcoat > 0), MicrofacetTransmission (spec_trans > 0), LambertianTransmission (thin). */
+typedef struct iile_disney {
+    float metallic, specular_tint, anisotropic, sheen, sheen_tint, clearcoat, clearcoat_gloss, spec_trans, flatness, diff_trans;
+    int32_t thin;
+    int32_t pad_;
+} iile_disney;
 
 /* ImageTexture<RGBSpectrum, Spectrum> over a UVMapping2D (src/textures/imagemap.h:78-112,
  * src/core/texture.cpp:170-180) with its MIPMap (src/core/mipmap.h:61-110): the pyramid is built on the
@@ -389,6 +405,9 @@ typedef struct iile_scene_desc {
     /* every light's power (appended last, as the quadrics were: a descriptor of the size before it is still read correctly while
      * it holds at most IILE_MAX_LIGHTS lights) */
     const float *light_power_all; /* [n_lights]: Power().y() of every light; read only when n_lights > IILE_MAX_LIGHTS */
+    /* the Disney materials' scalar parameters (appended last, as the two above were: a descriptor of the size before it is still read
+     * correctly while no material has type IILE_MAT_DISNEY) */
+    const iile_disney *disney;    /* [n_materials], or null; read only when some material has type IILE_MAT_DISNEY */
 } iile_scene_desc;
 
 /* One task of the IISPT render runner (IisptScheduleMonitorTask, src/integrators/iisptschedulemonitor.cpp:40-79): the

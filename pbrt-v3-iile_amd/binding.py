@@ -153,14 +153,14 @@ class _Sobol(ctypes.Structure):
 
 
 class SceneDesc(ctypes.Structure):
-    """The whole iile_scene_desc (include/iile_scene.h), light_power_all at its end."""
+    """The whole iile_scene_desc (include/iile_scene.h), light_power_all and disney at its end."""
     _fields_ = SceneDescHead._fields_ + [
         ("tri_n", c_vp), ("tri_uv", c_vp), ("prim_alpha", c_vp), ("n_spheres", c_i32), ("spheres", c_vp), ("n_materials", c_i32),
         ("materials", c_vp), ("n_lights", c_i32), ("lights", c_vp), ("n_env_dist", ctypes.c_int64), ("env_dist", c_vp),
         ("n_textures", c_i32), ("textures", c_vp), ("n_texels", ctypes.c_int64), ("texels", c_vp), ("ewa_lut", c_f32 * 128),
         ("film_filter_wide", c_i32), ("film_filter_table", c_f32 * 256), ("camera", Camera), ("film", FilmDesc), ("halton", _Halton),
         ("integrator", Integrator), ("probe", _ProbeSetup), ("sobol", _Sobol), ("n_quadrics", c_i32), ("quadrics", c_vp),
-        ("light_power_all", c_vp)]
+        ("light_power_all", c_vp), ("disney", c_vp)]
 
 
 MAX_LIGHTS = 8  # IILE_MAX_LIGHTS: the length of iile_integrator::light_power, not a limit on the lights of a scene
@@ -184,6 +184,13 @@ class Material(ctypes.Structure):
 
 MAT_MATTE, MAT_PLASTIC, MAT_UBER, MAT_MIRROR, MAT_GLASS, MAT_METAL, MAT_SUBSTRATE = range(7)
 MAT_TRANSLUCENT = 8  # (7 is not a material type)
+MAT_DISNEY = 10  # (9, like 7, is not a material type)
+
+
+class Disney(ctypes.Structure):
+    """iile_disney (include/iile_scene.h): the scalar parameters of a Disney material, iile_scene_desc::disney[material]."""
+    _fields_ = [(n, c_f32) for n in ("metallic specular_tint anisotropic sheen sheen_tint clearcoat clearcoat_gloss spec_trans "
+                                     "flatness diff_trans").split()] + [("thin", c_i32), ("pad_", c_i32)]
 QUADRIC_DISK, QUADRIC_CYLINDER = 0, 1
 PRIM_SPHERE, PRIM_FLIP, PRIM_QUADRIC = 1, 8, 32
 LIGHT_AREA_QUADRIC = 6
@@ -639,6 +646,16 @@ class HostScene:
         if host_lib().iile_host_scene_material(self._h, int(index), ctypes.byref(m)) != 0:
             raise RuntimeError(host_lib().iile_host_last_error().decode())
         return m
+
+    def disney(self, index):
+        """iile_disney number `index` of the scene (a copy): the scalar parameters of material `index`, a Disney material."""
+        d = self.scene_desc()
+        if not 0 <= int(index) < d.n_materials or self.material(index).type != MAT_DISNEY:
+            raise RuntimeError("HostScene.disney: material %d is not a Disney material" % int(index))
+        if not d.disney:
+            raise RuntimeError("the scene's descriptor has no disney table")
+        size = ctypes.sizeof(Disney)
+        return Disney.from_buffer_copy(ctypes.string_at(d.disney + int(index) * size, size))
 
     def prim_flags(self):
         """iile_scene_desc::prim_flags, in BVH order (a copy)."""

@@ -169,8 +169,13 @@ int check_scene_desc(const iile_scene_desc &d) {
         }
     }
     for (int i = 0; i < d.n_materials; ++i)
-        if ((d.materials[i].type < IILE_MAT_MATTE || d.materials[i].type > IILE_MAT_SUBSTRATE) && d.materials[i].type != IILE_MAT_TRANSLUCENT)
-            return api_fail(IILE_ERR_UNSUPPORTED, "unsupported material type");   // (7 among them)
+        if ((d.materials[i].type < IILE_MAT_MATTE || d.materials[i].type > IILE_MAT_SUBSTRATE) && d.materials[i].type != IILE_MAT_TRANSLUCENT &&
+            d.materials[i].type != IILE_MAT_DISNEY)
+            return api_fail(IILE_ERR_UNSUPPORTED, "unsupported material type");   // (7 and 9 among them)
+    // (disney lies behind the members an older caller's descriptor has: not touched unless a material is Disney's)
+    for (int i = 0; i < d.n_materials; ++i)
+        if (d.materials[i].type == IILE_MAT_DISNEY && !d.disney)
+            return api_fail(IILE_ERR_ARG, "disney is null: a Disney material reads its scalar parameters there");
     if (d.halton.n_dims > kMaxHaltonDims) return api_fail(IILE_ERR_UNSUPPORTED, "too many Halton dimensions");
     const int need_dims = 5 + 8 * d.integrator.max_depth + 1;
     if (d.halton.n_dims < need_dims) return api_fail(IILE_ERR_ARG, "Halton table covers too few dimensions for maxdepth");
@@ -296,12 +301,16 @@ void set_kernel_flags(const iile_scene_desc &d, DScene &S) {
         for (int t : material_textures(device_material(m, d.n_textures)))
             if (t >= 0) S.textured_materials = 1;
         if (m.type != IILE_MAT_MATTE && m.type != IILE_MAT_PLASTIC && m.type != IILE_MAT_METAL && m.type != IILE_MAT_SUBSTRATE &&
-            m.type != IILE_MAT_TRANSLUCENT)
+            m.type != IILE_MAT_TRANSLUCENT && m.type != IILE_MAT_DISNEY)
             S.has_specular = 1;   // (metal and substrate: one glossy reflection lobe each, metal.cpp:79, substrate.cpp:62; translucent:
-                                  //  diffuse and glossy lobes only, translucent.cpp:62-78)
+                                  //  diffuse and glossy lobes only, translucent.cpp:62-78; Disney: likewise, disney.cpp:505-587)
+        if (m.type == IILE_MAT_DISNEY) S.disney_build = 1;
         if ((m.type != IILE_MAT_MATTE && m.type != IILE_MAT_PLASTIC) || (m.type == IILE_MAT_MATTE && m.sigma != 0))
             S.extended_features = 1;
     }
+    // the Disney builds for any scene: the identity tests' switch (their other materials must render what the ordinary builds render)
+    if (std::getenv("IILE_DISNEY_BUILD")) S.disney_build = 1;
+    if (S.disney_build) S.extended_features = 1;
     S.all_lights_infinite = d.n_lights > 0 ? 1 : 0;
     for (int i = 0; i < d.n_lights; ++i)
         if (d.lights[i].type == IILE_LIGHT_INFINITE) S.has_infinite = 1;
@@ -504,8 +513,24 @@ int build_shapes(iile_scene *sc, const iile_scene_desc &d) {
 int build_materials(iile_scene *sc, const iile_scene_desc &d) {
     sc->ds.n_materials = d.n_materials;
     std::vector<DMaterial> mats(d.n_materials);
-    for (int i = 0; i < d.n_materials; ++i) mats[i] = device_material(d.materials[i], d.n_textures);
-    return upload(sc, mats.data(), mats.size(), &sc->ds.materials);
+    bool disney = false;
+    for (int i = 0; i < d.n_materials; ++i) {
+        mats[i] = device_material(d.materials[i], d.n_textures);
+        disney = disney || d.materials[i].type == IILE_MAT_DISNEY;
+    }
+    if (!disney) return upload(sc, mats.data(), mats.size(), &sc->ds.materials);
+    // (this function is the only place that sets DScene::materials: disney_table's reading past the array rests on that)
+    // the Disney materials' side table right behind the materials, entry for entry (disney_table, dscene.h; read at a hit on a
+    // Disney material only: make_bsdf_at, dbsdf.h)
+    static_assert(sizeof(DMaterial) % alignof(iile_disney) == 0, "the table behind the materials is aligned");
+    const size_t mat_bytes = mats.size() * sizeof(DMaterial), dz_bytes = size_t(d.n_materials) * sizeof(iile_disney);
+    std::vector<unsigned char> blob(mat_bytes + dz_bytes);
+    std::memcpy(blob.data(), mats.data(), mat_bytes);
+    std::memcpy(blob.data() + mat_bytes, d.disney, dz_bytes);
+    const unsigned char *dev = nullptr;
+    if (const int rc = upload(sc, blob.data(), blob.size(), &dev)) return rc;
+    sc->ds.materials = reinterpret_cast<const DMaterial *>(dev);
+    return IILE_OK;
 }
 
 // Textures: the host-built pyramids of the images, texels widened to float4 (one 16-byte load each); the procedural
@@ -903,7 +928,7 @@ static_assert(kQuadricDisk == IILE_QUADRIC_DISK && kQuadricCylinder == IILE_QUAD
               "quadric kind codes");
 static_assert(kMatMatte == IILE_MAT_MATTE && kMatPlastic == IILE_MAT_PLASTIC && kMatUber == IILE_MAT_UBER &&
                   kMatMirror == IILE_MAT_MIRROR && kMatGlass == IILE_MAT_GLASS && kMatMetal == IILE_MAT_METAL &&
-                  kMatSubstrate == IILE_MAT_SUBSTRATE && kMatTranslucent == IILE_MAT_TRANSLUCENT,
+                  kMatSubstrate == IILE_MAT_SUBSTRATE && kMatTranslucent == IILE_MAT_TRANSLUCENT && kMatDisney == IILE_MAT_DISNEY,
               "material type codes");
 static_assert(kShapeHitFloats == IILE_SHAPE_HIT_FLOATS, "shape hit record");
 static_assert(kTexImage == IILE_TEX_IMAGE && kTexScale == IILE_TEX_SCALE && kTexMix == IILE_TEX_MIX && kTexChecker2D == IILE_TEX_CHECKER2D &&

@@ -578,3 +578,392 @@ DEV F3 bsdf_sample_f(const Bsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *
     }
     return f;
 }
+
+// ===========================================================================
+// Disney (materials/disney.cpp) — the DIS builds of the kernels only
+// ===========================================================================
+// DisneyMaterial's BSDF holds up to eight BxDFs, five of them its own, and is much larger than every other material's: it lives in
+// a struct of its own behind the Bsdf the other materials fill, and the overloads below (make_bsdf_at, bsdf_f, bsdf_pdf,
+// bsdf_sample_f, n_nonspec on a DisneyBsdf) are what the DIS builds call. A hit on any other material goes through the functions
+// above unchanged; the builds without DIS never see this struct. Its lobes, in the order the material adds them (the order
+// BSDF::Sample_f counts them in and Pdf averages over), none of them tested for black:
+//   DisneyDiffuse, DisneyFakeSS (thin), DisneyRetro, DisneySheen (sheen > 0) — these four iff diffuseWeight > 0 —
+//   MicrofacetReflection (always), DisneyClearcoat (clearcoat > 0), MicrofacetTransmission (spectrans > 0), LambertianTransmission (thin)
+// The base's fields carry what they already mean: micro_r = c, (alpha, alpha_y) = DisneyMicrofacetDistribution(ax, ay), eta,
+// mtrans_t = spectrans sqrt(c), ltrans_t = difftrans / 2 c, has_micro / has_mtrans / has_ltrans, n_lobes; path_eta = 1 (BSDF(*si)).
+enum DisneyLobe : int { kDzDiffuse, kDzFakeSS, kDzRetro, kDzSheen, kDzMicro, kDzCoat, kDzMicroTrans, kDzLambertTrans };
+struct DisneyBsdf : Bsdf {
+    bool disney;               // the hit's material is Disney's; false: the Bsdf above is all there is
+    bool dz_diffuse;           // diffuseWeight > 0: DisneyDiffuse, DisneyRetro and, with the flags below, DisneyFakeSS / DisneySheen
+    bool dz_thin, dz_sheen, dz_coat;
+    bool dz_trans_smith;       // MicrofacetTransmission over a plain TrowbridgeReitzDistribution (thin): Smith's G, not the separable one
+    F3 r_diffuse, r_ss, r_retro, r_sheen;   // the four diffuse-type lobes' R
+    F3 cspec0;                 // DisneyFresnel(R0 = Cspec0, metallic, eta)
+    float metallic, rough;     // (rough: DisneyFakeSS's and DisneyRetro's roughness, as given)
+    float coat_w, coat_alpha;  // DisneyClearcoat(weight, gloss): alpha = Lerp(gloss, .1, .001)
+    float t_ax, t_ay;          // MicrofacetTransmission's distribution: (alpha, alpha_y) again, or thin's pair from the scaled roughness
+};
+template <bool DIS>
+struct bsdf_of { using type = Bsdf; };
+template <>
+struct bsdf_of<true> { using type = DisneyBsdf; };
+DEV float lerpf(float t, float a, float b) { return (1 - t) * a + t * b; }   // Lerp, pbrt.h:315
+DEV F3 lerp3(float t, F3 a, F3 b) { return (1 - t) * a + t * b; }            // Lerp, spectrum.h:482-484
+DEV float sqr(float x) { return x * x; }
+// SchlickWeight / FrSchlick / SchlickR0FromEta, disney.cpp:71-86
+DEV float schlick_weight(float cos_theta) {
+    const float m = clampf(1 - cos_theta, 0, 1);
+    return (m * m) * (m * m) * m;
+}
+DEV float fr_schlick(float r0, float cos_theta) { return lerpf(schlick_weight(cos_theta), r0, 1.f); }
+DEV F3 fr_schlick3(F3 r0, float cos_theta) { return lerp3(schlick_weight(cos_theta), r0, F3{1.f, 1.f, 1.f}); }
+DEV float schlick_r0_from_eta(float eta) { return sqr(eta - 1) / sqr(eta + 1); }
+
+// DisneyMaterial::ComputeScatteringFunctions, disney.cpp:475-588, with "scatterdistance" black and its ten scalar textures constants
+// (dz); c and the roughness arrive looked up at the hit (textured_material: kd, alpha)
+DEV void make_disney(const DMaterial &m, const iile_disney &dz, DisneyBsdf *b) {
+    b->disney = true;
+    b->mtype = kMatDisney;
+    b->t0 = b->kd = F3{0, 0, 0};
+    b->has_t0 = b->has_t1 = b->has_lambert = b->has_spec = b->has_blend = b->oren_nayar = false;
+    b->on_a = 1.f, b->on_b = 0.f;
+    b->path_eta = 1.f;   // BSDF(*si): eta = 1
+    const F3 c = clamp0(m.kd);
+    const float metallic_w = dz.metallic;
+    const float e = m.eta;
+    const float strans = dz.spec_trans;
+    const float diffuse_w = (1 - metallic_w) * (1 - strans);
+    const float dt = dz.diff_trans / 2;
+    const float rough = m.alpha;
+    const float lum = lum_y(c);
+    const F3 one = F3{1.f, 1.f, 1.f};
+    const F3 ctint = lum > 0 ? sdiv(c, lum) : one;
+    const float sheen_w = dz.sheen;
+    F3 csheen = F3{0, 0, 0};
+    if (sheen_w > 0) csheen = lerp3(dz.sheen_tint, one, ctint);
+    int n = 0;
+    b->dz_thin = dz.thin != 0;
+    b->dz_diffuse = diffuse_w > 0;
+    b->dz_sheen = false;
+    b->r_diffuse = b->r_ss = b->r_retro = b->r_sheen = F3{0, 0, 0};
+    b->rough = rough;
+    if (b->dz_diffuse) {
+        if (b->dz_thin) {
+            const float flat = dz.flatness;
+            b->r_diffuse = (diffuse_w * (1 - flat) * (1 - dt)) * c;
+            b->r_ss = (diffuse_w * flat * (1 - dt)) * c;
+            n += 2;
+        } else {
+            b->r_diffuse = diffuse_w * c;
+            ++n;
+        }
+        b->r_retro = diffuse_w * c;
+        ++n;
+        if (sheen_w > 0) {
+            b->dz_sheen = true;
+            b->r_sheen = (diffuse_w * sheen_w) * csheen;
+            ++n;
+        }
+    }
+    // `std::sqrt(1 - anisotropic * .9)`: the double overload
+    const float aspect = float(sqrt(1. - double(dz.anisotropic) * .9));
+    b->alpha = mx(.001f, sqr(rough) / aspect);
+    b->alpha_y = mx(.001f, sqr(rough) * aspect);
+    b->cspec0 = lerp3(metallic_w, schlick_r0_from_eta(e) * lerp3(dz.specular_tint, one, ctint), c);
+    b->metallic = metallic_w;
+    b->eta = e;
+    b->micro_r = c;
+    b->has_micro = true;
+    ++n;
+    b->dz_coat = dz.clearcoat > 0;
+    b->coat_w = dz.clearcoat;
+    b->coat_alpha = lerpf(dz.clearcoat_gloss, .1f, .001f);
+    if (b->dz_coat) ++n;
+    b->has_mtrans = strans > 0;
+    b->mtrans_t = F3{0, 0, 0};
+    b->t_ax = b->alpha, b->t_ay = b->alpha_y;
+    b->dz_trans_smith = false;
+    if (b->has_mtrans) {
+        b->mtrans_t = strans * F3{sqrtf(c.x), sqrtf(c.y), sqrtf(c.z)};
+        if (b->dz_thin) {  // the roughness scaled by the index of refraction, over a plain TrowbridgeReitzDistribution
+            const float rscaled = (0.65f * e - 0.35f) * rough;
+            b->t_ax = mx(.001f, sqr(rscaled) / aspect);
+            b->t_ay = mx(.001f, sqr(rscaled) * aspect);
+            b->dz_trans_smith = true;
+        }
+        ++n;
+    }
+    b->has_ltrans = b->dz_thin;
+    b->ltrans_t = F3{0, 0, 0};
+    if (b->dz_thin) {
+        b->ltrans_t = dt * c;
+        ++n;
+    }
+    b->n_lobes = n;
+}
+// The hit's BSDF in a DIS build: DisneyMaterial's, or the other materials' through make_bsdf. `material`: the material's index (its
+// entry of the scene's Disney table is read for a Disney material only)
+template <bool EXT, bool DIS>
+DEV typename bsdf_of<DIS>::type make_bsdf_at(const DScene &S, int material, const DMaterial &m, const Isect &is) {
+    if constexpr (!DIS) {
+        return make_bsdf<EXT>(m, is);
+    } else {
+        DisneyBsdf b;
+        if (m.type == kMatDisney) {
+            b.ns = is.sn;
+            b.ng = is.n;
+            b.ss = normalize(is.sdpdu);
+            b.ts = cross(b.ns, b.ss);
+            make_disney(m, disney_table(S)[material], &b);
+        } else {
+            static_cast<Bsdf &>(b) = make_bsdf<EXT>(m, is);
+            b.disney = false;
+        }
+        return b;
+    }
+}
+DEV int n_nonspec(const DisneyBsdf &b) { return b.disney ? b.n_lobes : n_nonspec(static_cast<const Bsdf &>(b)); }   // (no Disney lobe is specular)
+// DisneyDiffuse / DisneyFakeSS / DisneyRetro / DisneySheen ::f, disney.cpp:104-111, 138-154, 180-192, 218-225
+DEV F3 dz_diffuse_f(F3 R, F3 wo, F3 wi) {
+    const float Fo = schlick_weight(fabsf(wo.z)), Fi = schlick_weight(fabsf(wi.z));
+    return R * kInvPi * (1 - Fo / 2) * (1 - Fi / 2);
+}
+DEV F3 dz_fakess_f(F3 R, float roughness, F3 wo, F3 wi) {
+    F3 wh = wi + wo;
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return F3{0, 0, 0};
+    wh = normalize(wh);
+    const float cos_d = dot(wi, wh);
+    const float Fss90 = cos_d * cos_d * roughness;
+    const float Fo = schlick_weight(fabsf(wo.z)), Fi = schlick_weight(fabsf(wi.z));
+    const float Fss = lerpf(Fo, 1.f, Fss90) * lerpf(Fi, 1.f, Fss90);
+    const float ss = 1.25f * (Fss * (1 / (fabsf(wo.z) + fabsf(wi.z)) - .5f) + .5f);
+    return R * kInvPi * ss;
+}
+DEV F3 dz_retro_f(F3 R, float roughness, F3 wo, F3 wi) {
+    F3 wh = wi + wo;
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return F3{0, 0, 0};
+    wh = normalize(wh);
+    const float cos_d = dot(wi, wh);
+    const float Fo = schlick_weight(fabsf(wo.z)), Fi = schlick_weight(fabsf(wi.z));
+    const float Rr = 2 * roughness * cos_d * cos_d;
+    return R * kInvPi * Rr * (Fo + Fi + Fo * Fi * (Rr - 1));
+}
+DEV F3 dz_sheen_f(F3 R, F3 wo, F3 wi) {
+    F3 wh = wi + wo;
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return F3{0, 0, 0};
+    wh = normalize(wh);
+    return R * schlick_weight(dot(wi, wh));
+}
+// GTR1 / smithG_GGX, disney.cpp:251-262
+DEV float gtr1(float cos_theta, float alpha) {
+    const float alpha2 = alpha * alpha;
+    return (alpha2 - 1) / (kPi * log_f(alpha2) * (1 + (alpha2 - 1) * cos_theta * cos_theta));
+}
+DEV float smith_g_ggx(float cos_theta, float alpha) {
+    const float alpha2 = alpha * alpha;
+    const float cos2 = cos_theta * cos_theta;
+    return 1 / (cos_theta + sqrtf(alpha2 + cos2 - alpha2 * cos2));
+}
+// DisneyClearcoat::f / Pdf, disney.cpp:264-279, 305-318 (`.25 * weight * Gr * Fr * Dr` is a double product, rounded once)
+DEV F3 dz_coat_f(const DisneyBsdf &b, F3 wo, F3 wi) {
+    F3 wh = wi + wo;
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return F3{0, 0, 0};
+    wh = normalize(wh);
+    const float Dr = gtr1(fabsf(wh.z), b.coat_alpha);
+    const float Fr = fr_schlick(.04f, dot(wo, wh));
+    const float Gr = smith_g_ggx(fabsf(wo.z), .25f) * smith_g_ggx(fabsf(wi.z), .25f);
+    const float v = float(.25 * double(b.coat_w) * double(Gr) * double(Fr) * double(Dr));
+    return F3{v, v, v};
+}
+DEV float dz_coat_pdf(const DisneyBsdf &b, F3 wo, F3 wi) {
+    if (!same_hemisphere(wo, wi)) return 0;
+    F3 wh = wi + wo;
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return 0;
+    wh = normalize(wh);
+    const float Dr = gtr1(fabsf(wh.z), b.coat_alpha);
+    return Dr / (4 * dot(wo, wh));
+}
+// MicrofacetReflection::f (reflection.cpp:226-236) with R = c, DisneyMicrofacetDistribution (G = G1(wo) G1(wi), disney.cpp:356-359)
+// and DisneyFresnel::Evaluate (disney.cpp:334-337)
+DEV F3 dz_micro_f(const DisneyBsdf &b, F3 wo, F3 wi) {
+    const float cos_o = fabsf(wo.z), cos_i = fabsf(wi.z);
+    F3 wh = wi + wo;
+    if (cos_i == 0 || cos_o == 0) return F3{0, 0, 0};
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return F3{0, 0, 0};
+    wh = normalize(wh);
+    const float cos_h = dot(wi, wh);
+    const float fd = fr_dielectric(cos_h, 1.f, b.eta);
+    const F3 F = lerp3(b.metallic, F3{fd, fd, fd}, fr_schlick3(b.cspec0, cos_h));
+    const float G = tr_g1(wo, b.alpha, b.alpha_y) * tr_g1(wi, b.alpha, b.alpha_y);
+    return sdiv(b.micro_r * tr_d(wh, b.alpha, b.alpha_y) * G * F, 4 * cos_i * cos_o);
+}
+// MicrofacetTransmission::f / Pdf (reflection.cpp:244-266, 435-447) over the Disney BSDF's transmission distribution
+DEV F3 dz_mtrans_f(const DisneyBsdf &b, F3 wo, F3 wi) {
+    if (same_hemisphere(wo, wi)) return F3{0, 0, 0};
+    const float cos_o = wo.z, cos_i = wi.z;
+    if (cos_i == 0 || cos_o == 0) return F3{0, 0, 0};
+    const float eta_a = 1.f, eta_b = b.eta;
+    const float eta = wo.z > 0 ? (eta_b / eta_a) : (eta_a / eta_b);
+    F3 wh = normalize(wo + wi * eta);
+    if (wh.z < 0) wh = -wh;
+    const float F = fr_dielectric(dot(wo, wh), eta_a, eta_b);
+    const float sqrt_denom = dot(wo, wh) + eta * dot(wi, wh);
+    const float factor = 1 / eta;
+    const float omf = 1.f - F;
+    const float G = b.dz_trans_smith ? tr_g(wo, wi, b.t_ax, b.t_ay) : tr_g1(wo, b.t_ax, b.t_ay) * tr_g1(wi, b.t_ax, b.t_ay);
+    return F3{omf, omf, omf} * b.mtrans_t *
+           fabsf(tr_d(wh, b.t_ax, b.t_ay) * G * eta * eta * absdot(wi, wh) * absdot(wo, wh) * factor * factor /
+                 (cos_i * cos_o * sqrt_denom * sqrt_denom));
+}
+DEV float dz_mtrans_pdf(const DisneyBsdf &b, F3 wo, F3 wi) {
+    if (same_hemisphere(wo, wi)) return 0;
+    const float eta_a = 1.f, eta_b = b.eta;
+    const float eta = wo.z > 0 ? (eta_b / eta_a) : (eta_a / eta_b);
+    const F3 wh = normalize(wo + wi * eta);
+    const float sqrt_denom = dot(wo, wh) + eta * dot(wi, wh);
+    const float dwh_dwi = fabsf((eta * eta * dot(wi, wh)) / (sqrt_denom * sqrt_denom));
+    return tr_pdf(wo, wh, b.t_ax, b.t_ay) * dwh_dwi;
+}
+// one Disney lobe's f / Pdf
+DEV F3 dz_lobe_f(const DisneyBsdf &b, DisneyLobe l, F3 wo, F3 wi) {
+    switch (l) {
+    case kDzDiffuse: return dz_diffuse_f(b.r_diffuse, wo, wi);
+    case kDzFakeSS: return dz_fakess_f(b.r_ss, b.rough, wo, wi);
+    case kDzRetro: return dz_retro_f(b.r_retro, b.rough, wo, wi);
+    case kDzSheen: return dz_sheen_f(b.r_sheen, wo, wi);
+    case kDzMicro: return dz_micro_f(b, wo, wi);
+    case kDzCoat: return dz_coat_f(b, wo, wi);
+    case kDzMicroTrans: return dz_mtrans_f(b, wo, wi);
+    default: return ltrans_f(b);
+    }
+}
+DEV bool dz_has(const DisneyBsdf &b, DisneyLobe l) {
+    switch (l) {
+    case kDzDiffuse:
+    case kDzRetro: return b.dz_diffuse;
+    case kDzFakeSS: return b.dz_diffuse && b.dz_thin;
+    case kDzSheen: return b.dz_sheen;
+    case kDzMicro: return true;
+    case kDzCoat: return b.dz_coat;
+    case kDzMicroTrans: return b.has_mtrans;
+    default: return b.has_ltrans;
+    }
+}
+// the sum of BSDF::f over the Disney lobes on wi's side (BSDF_REFLECTION: the first six; BSDF_TRANSMISSION: the last two), in BxDF order
+DEV F3 dz_lobes_f(const DisneyBsdf &b, bool reflect, F3 wo, F3 wi) {
+    F3 f = F3{0, 0, 0};
+    if (reflect) {
+        if (b.dz_diffuse) {
+            f = f + dz_diffuse_f(b.r_diffuse, wo, wi);
+            if (b.dz_thin) f = f + dz_fakess_f(b.r_ss, b.rough, wo, wi);
+            f = f + dz_retro_f(b.r_retro, b.rough, wo, wi);
+            if (b.dz_sheen) f = f + dz_sheen_f(b.r_sheen, wo, wi);
+        }
+        f = f + dz_micro_f(b, wo, wi);
+        if (b.dz_coat) f = f + dz_coat_f(b, wo, wi);
+    } else {
+        if (b.has_mtrans) f = f + dz_mtrans_f(b, wo, wi);
+        if (b.has_ltrans) f = f + ltrans_f(b);
+    }
+    return f;
+}
+// the sum of the Disney lobes' Pdf in BxDF order, `skip` left out (-1: none). The four diffuse-type lobes have BxDF::Pdf, the
+// cosine density on wo's side (reflection.cpp:387-389): it enters once per such lobe.
+DEV float dz_lobes_pdf(const DisneyBsdf &b, int skip, F3 wo, F3 wi, float pdf) {
+    const float cosine = lambert_pdf(wo, wi);
+#pragma unroll
+    for (int l = kDzDiffuse; l <= kDzSheen; ++l)
+        if (l != skip && dz_has(b, DisneyLobe(l))) pdf += cosine;
+    if (skip != kDzMicro) pdf += micro_pdf(b, wo, wi);
+    if (skip != kDzCoat && b.dz_coat) pdf += dz_coat_pdf(b, wo, wi);
+    if (skip != kDzMicroTrans && b.has_mtrans) pdf += dz_mtrans_pdf(b, wo, wi);
+    if (skip != kDzLambertTrans && b.has_ltrans) pdf += ltrans_pdf(wo, wi);
+    return pdf;
+}
+// BSDF::f / Pdf / Sample_f (reflection.cpp:686-699, 786-801, 719-784) in a DIS build
+DEV F3 bsdf_f(const DisneyBsdf &b, F3 woW, F3 wiW) {
+    if (!b.disney) return bsdf_f(static_cast<const Bsdf &>(b), woW, wiW);
+    const F3 wi = to_local(b, wiW), wo = to_local(b, woW);
+    if (wo.z == 0) return F3{0, 0, 0};
+    const bool reflect = dot(wiW, b.ng) * dot(woW, b.ng) > 0;
+    return dz_lobes_f(b, reflect, wo, wi);
+}
+DEV float bsdf_pdf(const DisneyBsdf &b, F3 woW, F3 wiW) {
+    if (!b.disney) return bsdf_pdf(static_cast<const Bsdf &>(b), woW, wiW);
+    const F3 wo = to_local(b, woW), wi = to_local(b, wiW);
+    if (wo.z == 0) return 0.f;
+    return dz_lobes_pdf(b, -1, wo, wi, 0.f) / b.n_lobes;   // (n_lobes >= 1: MicrofacetReflection is always there)
+}
+DEV F3 bsdf_sample_f(const DisneyBsdf &b, F3 woW, F3 *wiW, float u0, float u1, float *pdf, const bool allow_specular = false,
+                     bool *sampled_specular = nullptr, bool *sampled_transmission = nullptr) {
+    if (!b.disney) return bsdf_sample_f(static_cast<const Bsdf &>(b), woW, wiW, u0, u1, pdf, allow_specular, sampled_specular, sampled_transmission);
+    if (sampled_specular) *sampled_specular = false;
+    if (sampled_transmission) *sampled_transmission = false;
+    const int matching = b.n_lobes;
+    int comp = int(floorf(u0 * matching));
+    if (comp > matching - 1) comp = matching - 1;
+    // the comp-th present lobe in BxDF order
+    int pick = kDzLambertTrans, count = comp;
+    bool found = false;
+#pragma unroll
+    for (int l = kDzDiffuse; l <= kDzLambertTrans; ++l)
+        if (!found && dz_has(b, DisneyLobe(l)) && count-- == 0) pick = l, found = true;
+    const float ur0 = mn(u0 * matching - comp, kOneMinusEpsilon);
+    const F3 wo = to_local(b, woW);
+    if (wo.z == 0) return F3{0, 0, 0};
+    *pdf = 0;
+    F3 wi = F3{0, 0, 0}, f;
+    if (pick <= kDzSheen) {  // BxDF::Sample_f, reflection.cpp:378-385
+        wi = cosine_sample_hemisphere(ur0, u1);
+        if (wo.z < 0) wi.z *= -1;
+        *pdf = lambert_pdf(wo, wi);
+        f = dz_lobe_f(b, DisneyLobe(pick), wo, wi);
+    } else if (pick == kDzMicro) {  // MicrofacetReflection::Sample_f, reflection.cpp:405-417
+        const F3 wh = tr_sample_wh(wo, ur0, u1, b.alpha, b.alpha_y);
+        wi = -wo + 2 * dot(wo, wh) * wh;
+        if (!same_hemisphere(wo, wi))
+            f = F3{0, 0, 0};
+        else {
+            *pdf = tr_pdf(wo, wh, b.alpha, b.alpha_y) / (4 * dot(wo, wh));
+            f = dz_micro_f(b, wo, wi);
+        }
+    } else if (pick == kDzCoat) {  // DisneyClearcoat::Sample_f, disney.cpp:281-303: alpha fixed at .25
+        const float alpha2 = .25f * .25f;
+        const float cos_t = sqrtf(mx(0.f, (1 - powf(alpha2, 1 - ur0)) / (1 - alpha2)));
+        const float sin_t = sqrtf(mx(0.f, 1 - cos_t * cos_t));
+        const float phi = 2 * kPi * u1;
+        float sp, cp;
+        sincos_f(phi, &sp, &cp);
+        F3 wh = F3{sin_t * cp, sin_t * sp, cos_t};   // SphericalDirection, geometry.h:1427-1431
+        if (!same_hemisphere(wo, wh)) wh = -wh;
+        wi = -wo + 2 * dot(wo, wh) * wh;
+        if (!same_hemisphere(wo, wi))
+            f = F3{0, 0, 0};   // `return Spectrum(0.f)`, *pdf untouched
+        else {
+            *pdf = dz_coat_pdf(b, wo, wi);
+            f = dz_coat_f(b, wo, wi);
+        }
+    } else if (pick == kDzMicroTrans) {  // MicrofacetTransmission::Sample_f, reflection.cpp:425-433
+        const F3 wh = tr_sample_wh(wo, ur0, u1, b.t_ax, b.t_ay);
+        const float eta_a = 1.f, eta_b = b.eta;
+        const float eta = wo.z > 0 ? (eta_a / eta_b) : (eta_b / eta_a);
+        if (!refract_dir(wo, wh, eta, &wi)) return F3{0, 0, 0};  // `return 0`, pdf stays 0
+        *pdf = dz_mtrans_pdf(b, wo, wi);
+        f = dz_mtrans_f(b, wo, wi);
+    } else {  // LambertianTransmission::Sample_f, reflection.cpp:391-398
+        wi = cosine_sample_hemisphere(ur0, u1);
+        if (wo.z > 0) wi.z *= -1;
+        *pdf = ltrans_pdf(wo, wi);
+        f = ltrans_f(b);
+    }
+    if (*pdf == 0) return F3{0, 0, 0};
+    *wiW = to_world(b, wi);
+    if (matching > 1) {
+        *pdf = dz_lobes_pdf(b, pick, wo, wi, *pdf);
+        *pdf /= matching;
+        const bool reflect = dot(*wiW, b.ng) * dot(woW, b.ng) > 0;
+        f = dz_lobes_f(b, reflect, wo, wi);
+    }
+    if (sampled_transmission) *sampled_transmission = false;   // (read only together with sampled_specular: path.cpp:151)
+    return f;
+}

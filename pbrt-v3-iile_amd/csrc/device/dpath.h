@@ -944,8 +944,9 @@ DEV void triangle_interaction(const DScene &S, int prim, uint32_t flags, F3 p0, 
 // needs it). EXT = false: the plain build, whose one light is an emitting sphere, *lsp (both wave-uniform, see uniform_entry).
 // COUNT: the instrumented build, which traces every MIS ray (no can_reach skip) and counts Shape::Pdf's Triangle::Intersect
 // calls in *n_pdf_tests / *n_pdf_hits.
-template <bool EXT, bool COUNT>
-DEV uint32_t estimate_direct_request(const DScene &S, const DLight &lt, const DSphere *lsp, const Isect &is, const Bsdf &bsdf, float ul0,
+// BSDF: Bsdf, or the DIS builds' DisneyBsdf (dbsdf.h).
+template <bool EXT, bool COUNT, class BSDF>
+DEV uint32_t estimate_direct_request(const DScene &S, const DLight &lt, const DSphere *lsp, const Isect &is, const BSDF &bsdf, float ul0,
                                      float ul1, float us0, float us1, F3 &so, F3 &sd, F3 &A, F3 &mo, F3 &md, F3 &Bc,
                                      unsigned long long *n_pdf_tests, unsigned long long *n_pdf_hits) {
     uint32_t nee_flags = 0;

@@ -35,7 +35,7 @@ struct DQuadric {
     int reverse_orientation, swaps_handedness;
 };
 enum { kMatMatte = 0, kMatPlastic = 1, kMatUber = 2, kMatMirror = 3, kMatGlass = 4, kMatMetal = 5, kMatSubstrate = 6,
-       kMatTranslucent = 8 };  // = IILE_MAT_* (checked in api_scene.hip)
+       kMatTranslucent = 8, kMatDisney = 10 };  // = IILE_MAT_* (checked in api_scene.hip)
 // (16-byte aligned, and the fields every hit reads first: (type, kd) and (ks, alpha) are one float4 each, see make_bsdf in dbsdf.h)
 struct alignas(16) DMaterial {
     int type;
@@ -148,7 +148,7 @@ struct DScene {
     const uint32_t *pixel_offsets;  // [128*128] Halton index offset of pixel (x mod 128, y mod 128)
     const DSphere *spheres;
     const DQuadric *quadrics;  // disks and cylinders
-    const DMaterial *materials;
+    const DMaterial *materials;  // [n_materials]; in a scene with a Disney material followed by iile_disney[n_materials] (disney_table)
     const DLight *lights;
     const DTexture *textures;  // image textures (k_shade<.., TEX = true>)
     const float4 *texels;
@@ -161,6 +161,9 @@ struct DScene {
     int n_perms;              // u16 entries of `perms`
     float root_box[6];        // bounds of the root node (min.xyz, max.xyz)
     int root_ref;             // >= 0: wide record; < 0: ~first primitive of a single-leaf tree
+    // (in the four bytes that were padding before the pointer below, so that every other member sits where it sat)
+    int disney_build;         // some material is Disney's, or IILE_DISNEY_BUILD is set: the DIS builds of the kernels that make a BSDF.
+                              // A scene with a Disney material keeps the iile_disney table [n_materials] right behind `materials`
     // The top levels of the four-wide tree once more (breadth first, at most kMaxTop records of 8 float4): every block of a
     // traversal kernel keeps a copy in LDS, and references between them are kTopFlag | slot (dtrav.h, load_wide4).
     const float4 *top4;
@@ -222,6 +225,11 @@ struct DScene {
     int max_depth;
     float rr_threshold;
 };
+static_assert(sizeof(DScene) == 672, "DScene keeps its size: the kernels take it by value, and their register allocation follows its layout");
+// the Disney materials' scalar parameters, entry for entry with the materials (only in a scene that has a Disney material)
+inline __host__ __device__ const iile_disney *disney_table(const DScene &S) {
+    return reinterpret_cast<const iile_disney *>(S.materials + S.n_materials);
+}
 // a copy of the scene constants whose sampler, sample range or kernels are not the frame's own carries no sample table (host side)
 inline void clear_sample_table(DScene *S) {
     S->stab_cam = S->stab_lens = nullptr;

@@ -17,6 +17,7 @@
 // level and on the heap layout of the process. This pass costs two orders of magnitude less than the probe pass and
 // the network it sits between; it is written for exactness (bit for bit the oracle's restatement).
 // Random numbers: every film pixel draws from its own PCG32 stream RNG(rng_seed + pixel rank) (iile_iispt_task).
+#include <type_traits>
 #include "dpath.h"
 #include "api_common.h"
 
@@ -67,8 +68,11 @@ DEV void item_pixel(const iile_iispt_task &T, int nx, int n_hemi, int item, int 
 }
 // the vertex of a finished item again: SurfaceInteraction + BSDF from its hit record, exactly as k_iispt_vertex built
 // them (ComputeScatteringFunctions is a pure function of the hit, the ray and — for textures — the camera sample)
+// (BSDF: Bsdf, or the Disney builds' DisneyBsdf)
+template <class BSDF>
 DEV void vertex_state(const DScene &S, const float4 o4, const float4 d4, const float4 h4, const float4 pf4, bool camera_ray_hit, Isect *is,
-                      Bsdf *bsdf, int *material_out) {
+                      BSDF *bsdf, int *material_out) {
+    constexpr bool DIS = std::is_same<BSDF, DisneyBsdf>::value;
     const int prim = int(f2b(h4.x));
     const F3 ro = F3{o4.x, o4.y, o4.z}, rd = F3{d4.x, d4.y, d4.z};
     const float4 v0 = S.tri_verts[3 * size_t(prim)], v1 = S.tri_verts[3 * size_t(prim) + 1], v2 = S.tri_verts[3 * size_t(prim) + 2];
@@ -90,9 +94,9 @@ DEV void vertex_state(const DScene &S, const float4 o4, const float4 d4, const f
         if (camera_ray_hit) td = compute_differentials(*is, camera_differentials(S, pf4.x, pf4.y, pf4.z, pf4.w, ro, rd), &dpdx, &dpdy);
         if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, is);
         const DMaterial mm = textured_material(S, m0, *is, td, dpdx, dpdy);
-        *bsdf = make_bsdf<true>(mm, *is);
+        *bsdf = make_bsdf_at<true, DIS>(S, material, mm, *is);
     } else {
-        *bsdf = make_bsdf<true>(m0, *is);
+        *bsdf = make_bsdf_at<true, DIS>(S, material, m0, *is);
     }
 }
 }  // namespace
@@ -147,7 +151,8 @@ __global__ __launch_bounds__(kIisptBlock) void k_iispt_trace(DScene S, const Iis
     }
 }
 
-// one iteration of find_intersection's loop for every active item
+// one iteration of find_intersection's loop for every active item (DIS: the scene's Disney build, DScene::disney_build)
+template <bool DIS>
 __global__ __launch_bounds__(kIisptBlock) void k_iispt_vertex(DScene S, const IisptJob *jobs) {
     const iile_iispt_task T = jobs[blockIdx.y].T;
     const IisptItems I = jobs[blockIdx.y].I;
@@ -166,7 +171,7 @@ __global__ __launch_bounds__(kIisptBlock) void k_iispt_vertex(DScene S, const Ii
             state = kItemNoSurface;  // no intersection: find_intersection returns false
         } else {
             Isect is;
-            Bsdf bsdf;
+            typename bsdf_of<DIS>::type bsdf;
             int material;
             vertex_state(S, o4, d4, h4, I.pf[item], bounce == 0, &is, &bsdf, &material);
             if (material < 0) {  // `if (!isect.bsdf)`: skip this intersection
@@ -319,7 +324,8 @@ DEV F3 light_sample_dir(const DHemiCam &hc, const float *nn, F3 wi, int hemi, co
     return F3{0, 0, 0};
 }
 // estimate_direct, iisptrenderrunner.cpp:16-140
-DEV F3 estimate_direct_nn(const Isect &it, const Bsdf &bsdf, int rx, int ry, const DHemiCam &hc, const float *nn, int hemi, const float *jac, Pcg &rng) {
+template <class BSDF>
+DEV F3 estimate_direct_nn(const Isect &it, const BSDF &bsdf, int rx, int ry, const DHemiCam &hc, const float *nn, int hemi, const float *jac, Pcg &rng) {
     F3 Ld = F3{0, 0, 0};
     F3 wi = F3{0, 0, 0};
     const float light_pdf = float(1.0 / 6.28);
@@ -351,6 +357,7 @@ DEV F3 estimate_direct_nn(const Isect &it, const Bsdf &bsdf, int rx, int ry, con
 }
 }  // namespace
 
+template <bool DIS>
 __global__ __launch_bounds__(kIisptBlock) void k_iispt_gather(DScene S, const IisptJob *jobs, const float *jac) {
     const iile_iispt_task T = jobs[blockIdx.y].T;
     const IisptItems I = jobs[blockIdx.y].I;
@@ -371,7 +378,7 @@ __global__ __launch_bounds__(kIisptBlock) void k_iispt_gather(DScene S, const Ii
         const float4 o4 = I.ro[item], d4 = I.rd[item], beta4 = I.beta[item];
         if (item_has_vertex(d4, beta4)) {
             Isect f_is;
-            Bsdf f_bsdf;
+            typename bsdf_of<DIS>::type f_bsdf;
             int material;
             vertex_state(S, o4, d4, I.hit[item], I.pf[item], ((f2b(d4.w) >> 8) & 0xffu) == 0u, &f_is, &f_bsdf, &material);
             const F3 f_ray_d = F3{d4.x, d4.y, d4.z}, f_beta = F3{beta4.x, beta4.y, beta4.z};
@@ -484,7 +491,10 @@ int first_hits_rounds(const DScene &S, const IisptJob *jobs, int n_jobs, int max
     for (int bounce = 0; bounce < 24; ++bounce) {
         HIP_TRY(hipMemsetAsync(n_active, 0, sizeof(uint32_t), cfg.stream));
         hipLaunchKernelGGL(k_iispt_trace, grid, dim3(kIisptBlock), 0, cfg.stream, S, jobs, spill);
-        hipLaunchKernelGGL(k_iispt_vertex, grid, dim3(kIisptBlock), 0, cfg.stream, S, jobs);
+        if (S.disney_build)
+            hipLaunchKernelGGL(k_iispt_vertex<true>, grid, dim3(kIisptBlock), 0, cfg.stream, S, jobs);
+        else
+            hipLaunchKernelGGL(k_iispt_vertex<false>, grid, dim3(kIisptBlock), 0, cfg.stream, S, jobs);
         uint32_t host_active = 0;
         HIP_TRY(hipMemcpyAsync(&host_active, n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, cfg.stream));
         HIP_TRY(hipStreamSynchronize(cfg.stream));
@@ -511,7 +521,10 @@ void launch_reference_points(const DScene &S, int n, const float4 *ro, const flo
                        pos3, dir3);
 }
 void launch_iispt_gather(const DScene &S, const IisptJob *jobs, int n_jobs, int max_pixels, const float *jac, const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_iispt_gather, job_grid(max_pixels, n_jobs, cfg), dim3(kIisptBlock), 0, cfg.stream, S, jobs, jac);
+    if (S.disney_build)
+        hipLaunchKernelGGL(k_iispt_gather<true>, job_grid(max_pixels, n_jobs, cfg), dim3(kIisptBlock), 0, cfg.stream, S, jobs, jac);
+    else
+        hipLaunchKernelGGL(k_iispt_gather<false>, job_grid(max_pixels, n_jobs, cfg), dim3(kIisptBlock), 0, cfg.stream, S, jobs, jac);
 }
 
 // IisptFilmMonitor::add_n_samples (src/integrators/iisptfilmmonitor.cpp:47-72) for every pixel of every task of a batch: the

@@ -20,6 +20,7 @@
 // SpecularReflection and a SpecularTransmission lobe (glass.cpp:62-90) and both recursions fire —: scenes with glass do not take
 // this wavefront but k_direct_tree below, one thread per pixel walking the tree depth first (round 3 rendered glass black beyond
 // its direct light, which the round-3 advisor showed to be wrong).
+#include <type_traits>
 #include "dfilm.h"  // direct_film_add: the render loop's guards and the add into the double film, for k_direct_fold and k_direct_tree
 
 namespace iile {
@@ -92,7 +93,8 @@ __global__ __launch_bounds__(kBlock) void k_direct_generate(DScene S, PassDesc P
 #ifndef IILE_DIRECT_SHADE_WAVES
 #define IILE_DIRECT_SHADE_WAVES 2  // waves per SIMD the register allocation aims at
 #endif
-template <bool TEX>
+// DIS: the scene's Disney build (DScene::disney_build; textured flavour only)
+template <bool TEX, bool DIS = false>
 __global__ __launch_bounds__(kBlock, IILE_DIRECT_SHADE_WAVES) void k_direct_shade(DScene S, PassDesc P, PassBuffers B, int depth, uint32_t plane) {
     const uint32_t count = B.counts[kCntShade + depth];
     const float4 *ro = B.ray_o[depth & 1], *rd = B.ray_d[depth & 1];
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(kBlock, IILE_DIRECT_SHADE_WAVES) void k_direct_shad
         const uint32_t slot = ent & ((1u << kSlotBits) - 1u);
         uint32_t pid = 0;
         Isect is;
-        Bsdf bsdf;
+        typename bsdf_of<DIS>::type bsdf;
         F3 ray_d = F3{0, 0, 1};
         bool lit_surface = false;  // a surface with a non-specular lobe: EstimateDirect can return something
         DPcg stream{0, 1};
@@ -159,9 +161,9 @@ __global__ __launch_bounds__(kBlock, IILE_DIRECT_SHADE_WAVES) void k_direct_shad
             }
             if (TEX && S.textured_materials && mat_tex) {
                 if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, &is);
-                bsdf = make_bsdf<true>(textured_material(S, m0, is, td, dpdx, dpdy), is);
+                bsdf = make_bsdf_at<true, DIS>(S, material, textured_material(S, m0, is, td, dpdx, dpdy), is);
             } else {
-                bsdf = make_bsdf<true>(m0, is);
+                bsdf = make_bsdf_at<true, DIS>(S, material, m0, is);
             }
             // L += isect.Le(wo)
             if (light >= 0) {
@@ -368,18 +370,20 @@ TREE_CALL void tree_interaction(const DScene &S, int prim, F3 ro, F3 rd, float b
         triangle_interaction(S, prim, flags, F3{v0.x, v0.y, v0.z}, F3{v1.x, v1.y, v1.z}, F3{v2.x, v2.y, v2.z}, rd, b0, b1, b2, is);
     }
 }
-template <bool TEX>
-TREE_CALL void tree_bsdf(const DScene &S, int material, const TexDiff &td, F3 dpdx, F3 dpdy, Isect *is, Bsdf *bsdf) {
+template <bool TEX, class BSDF>
+TREE_CALL void tree_bsdf(const DScene &S, int material, const TexDiff &td, F3 dpdx, F3 dpdy, Isect *is, BSDF *bsdf) {
+    constexpr bool DIS = std::is_same<BSDF, DisneyBsdf>::value;
     const DMaterial &m0 = S.materials[material];
     const bool mat_tex = m0.kd_tex >= 0 || m0.ks_tex >= 0 || m0.kr_tex >= 0 || m0.kt_tex >= 0 || m0.bump_tex >= 0 || m0.rough_tex >= 0 || m0.sigma_tex >= 0 || m0.opacity_tex >= 0 || m0.rough_tex_v >= 0;
     if (TEX && S.textured_materials && mat_tex) {
         if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, is);
-        *bsdf = make_bsdf<true>(textured_material(S, m0, *is, td, dpdx, dpdy), *is);
+        *bsdf = make_bsdf_at<true, DIS>(S, material, textured_material(S, m0, *is, td, dpdx, dpdy), *is);
     } else {
-        *bsdf = make_bsdf<true>(m0, *is);
+        *bsdf = make_bsdf_at<true, DIS>(S, material, m0, *is);
     }
 }
-TREE_CALL uint32_t tree_light_request(const DScene &S, int li, const Isect &is, const Bsdf &bsdf, float ul0, float ul1, float us0, float us1, F3 *so,
+template <class BSDF>
+TREE_CALL uint32_t tree_light_request(const DScene &S, int li, const Isect &is, const BSDF &bsdf, float ul0, float ul1, float us0, float us1, F3 *so,
                                       F3 *sd, F3 *A, F3 *mo, F3 *md, F3 *Bc) {
     const DLight &lt = S.lights[li];
     unsigned long long nt = 0, nh = 0;
@@ -408,7 +412,7 @@ struct TreeLevel {
 };
 }  // namespace
 
-template <bool TEX, int NT>
+template <bool TEX, int NT, bool DIS = false>
 __global__ __launch_bounds__(kBlock, 1) void k_direct_tree(DScene S, PassDesc P, PassBuffers B, double *film_rgbw) {
     __shared__ int lds_stack[kWavesPerBlock][2 * kLdsStackDepth][64];
     lds_int *my_stack = (lds_int *)&lds_stack[threadIdx.x >> 6][0][threadIdx.x & 63];
@@ -457,7 +461,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_direct_tree(DScene S, PassDesc P,
                 TexDiff td = TexDiff{0, 0, 0, 0};
                 F3 dpdx = F3{0, 0, 0}, dpdy = F3{0, 0, 0};
                 if (TEX && has_diff) td = compute_differentials(is, rdiff, &dpdx, &dpdy);
-                Bsdf bsdf;
+                typename bsdf_of<DIS>::type bsdf;
                 tree_bsdf<TEX>(S, material, td, dpdx, dpdy, &is, &bsdf);
                 TreeLevel<NT> &me = lv[depth];
                 me.L = F3{0, 0, 0};
@@ -664,7 +668,12 @@ __global__ __launch_bounds__(kBlock, 1) void k_direct_tree(DScene S, PassDesc P,
 void launch_direct_tree(const DScene &S, const PassDesc &P, const PassBuffers &B, double *film_rgbw, const LaunchCfg &cfg) {
     const dim3 grid(grid_blocks(P.n_paths, cfg.n_cus, 4));
     const bool tex = S.textured_materials || S.n_textures > 0;
-    if (S.has_uber_trans) {
+    if (S.disney_build) {  // a scene with a Disney material: the textured flavour's Disney builds
+        if (S.has_uber_trans)
+            hipLaunchKernelGGL((k_direct_tree<true, 2, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, film_rgbw);
+        else
+            hipLaunchKernelGGL((k_direct_tree<true, 1, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, film_rgbw);
+    } else if (S.has_uber_trans) {
         if (tex)
             hipLaunchKernelGGL((k_direct_tree<true, 2>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, film_rgbw);
         else
@@ -680,7 +689,9 @@ void launch_direct_generate(const DScene &S, const PassDesc &P, const PassBuffer
 }
 void launch_direct_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int depth, uint32_t max_rays, const LaunchCfg &cfg) {
     const dim3 grid(grid_blocks(max_rays, cfg.n_cus, 2));
-    if (S.textured_materials)
+    if (S.disney_build)
+        hipLaunchKernelGGL((k_direct_shade<true, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, depth, B.queue_cap);
+    else if (S.textured_materials)
         hipLaunchKernelGGL((k_direct_shade<true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, depth, B.queue_cap);
     else
         hipLaunchKernelGGL((k_direct_shade<false>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, depth, B.queue_cap);

@@ -36,6 +36,8 @@ void launch_camera(const DScene &S, int n, const float *pfilm, const float *plen
 // BSDF in a canonical frame (ns = +z, ss = +x; the geometric normal ng, +z unless a test tilts it). sample == 0: out = {f.xyz, pdf}
 // for (wo, wi); sample == 1: out = {wi.xyz, f.xyz, pdf} for (wo, u); sample == 2: the same sample with the specular lobes allowed
 // (BSDF_ALL), out = {wi.xyz, f.xyz, pdf, sampled_specular, sampled_transmission}, the two flags as 0 or 1.
+// DIS: the scene's Disney build (DScene::disney_build).
+template <bool DIS>
 __global__ void k_bsdf_probe(DScene S, int n, int mat, const float *wo, const float *wi_or_u, int sample, float *out, float ngx,
                              float ngy, float ngz) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -45,7 +47,7 @@ __global__ void k_bsdf_probe(DScene S, int n, int mat, const float *wo, const fl
     is.n = F3{ngx, ngy, ngz};
     is.sdpdu = F3{1, 0, 0};
     is.p = is.perr = is.wo = F3{0, 0, 0};
-    Bsdf b = make_bsdf(S.materials[mat], is);
+    auto b = make_bsdf_at<true, DIS>(S, mat, S.materials[mat], is);
     b.ss = F3{1, 0, 0};
     b.ts = cross(b.ns, b.ss);
     const F3 w = F3{wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]};
@@ -75,8 +77,12 @@ __global__ void k_bsdf_probe(DScene S, int n, int mat, const float *wo, const fl
 }
 void launch_bsdf_probe(const DScene &S, int n, int mat, const float *wo, const float *wi_or_u, int sample,
                        float *out, const float ng[3], const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_bsdf_probe, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, mat, wo, wi_or_u, sample,
-                       out, ng[0], ng[1], ng[2]);
+    if (S.disney_build)
+        hipLaunchKernelGGL(k_bsdf_probe<true>, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, mat, wo, wi_or_u, sample, out, ng[0], ng[1],
+                           ng[2]);
+    else
+        hipLaunchKernelGGL(k_bsdf_probe<false>, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, mat, wo, wi_or_u, sample, out, ng[0], ng[1],
+                           ng[2]);
 }
 __global__ void k_trig_probe(int n, const float *x, float *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

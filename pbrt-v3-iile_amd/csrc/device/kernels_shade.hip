@@ -142,7 +142,10 @@ __global__ void k_sample_table_read(DScene S, int n, const int *px, const int *p
 #ifndef IILE_SHADE_WAVES_TEX
 #define IILE_SHADE_WAVES_TEX 3
 #endif
-constexpr int shade_waves(bool tex) { return tex ? IILE_SHADE_WAVES_TEX : IILE_SHADE_WAVES; }
+#ifndef IILE_SHADE_WAVES_DISNEY
+#define IILE_SHADE_WAVES_DISNEY 2
+#endif
+constexpr int shade_waves(bool tex, bool disney = false) { return disney ? IILE_SHADE_WAVES_DISNEY : (tex ? IILE_SHADE_WAVES_TEX : IILE_SHADE_WAVES); }
 // TAB: the scene has a sample table (DScene::stab_*; never an instrumented build, never Sobol'). A wavefront whose valid lanes all
 //   sit at dimension 5 + 7 bounce — every one unless a specular-only vertex or a roulette draw made its lanes disagree — reads its
 //   vertex's eight samples as one 32-byte record; `hidx` is then the sample slot, not the Halton index. The other wavefronts run
@@ -150,9 +153,13 @@ constexpr int shade_waves(bool tex) { return tex ? IILE_SHADE_WAVES_TEX : IILE_S
 #ifndef IILE_SHADE_TAB_REREAD
 #define IILE_SHADE_TAB_REREAD 0  // 1: the continuation reads its samples from the record again instead of keeping them in registers
 #endif
-template <bool COUNT, bool EXT, bool TEX, bool TAB = false>
-__global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, PassDesc P, PassBuffers B, int bounce, uint32_t plane) {
+// DIS: the scene has a Disney material (DScene::disney_build): the vertex's BSDF is a DisneyBsdf (dbsdf.h), always in the textured
+//   flavour. The instrumented build includes it.
+template <bool COUNT, bool EXT, bool TEX, bool TAB = false, bool DIS = false>
+__global__ __launch_bounds__(kBlock, shade_waves(TEX, DIS)) void k_shade(DScene S, PassDesc P, PassBuffers B, int bounce, uint32_t plane) {
     static_assert(!(TAB && COUNT), "the instrumented build keeps the digit chains");
+    static_assert(!DIS || (EXT && TEX && !COUNT), "the Disney builds are textured ones");
+    constexpr bool DZ = DIS || COUNT;
     typename std::conditional<TAB, const uint16_t *, lds_u16 *>::type s_perms;
     if constexpr (TAB) {
         s_perms = S.perms;
@@ -233,7 +240,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
         float4 rec_a = make_float4(0, 0, 0, 0), rec_b = make_float4(0, 0, 0, 0);
         auto chain_index = [&]() { return TAB ? slot_halton_index(S, hidx) : hidx; };  // what the digit chains start from
         Isect is;
-        Bsdf bsdf;
+        typename bsdf_of<DZ>::type bsdf;
         F3 beta = F3{0, 0, 0}, ray_d = F3{0, 0, 1};
         uint32_t state_next = 0;
         {
@@ -371,12 +378,12 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
                             }
                             if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, &is);  // `if (bumpMap) Bump(bumpMap, si)` comes first
                             const DMaterial mm = textured_material(S, m0, is, td, dpdx, dpdy);
-                            bsdf = make_bsdf<EXT>(mm, is);
+                            bsdf = make_bsdf_at<EXT, DZ>(S, material, mm, is);
                         } else {
-                            bsdf = make_bsdf<EXT>(m0, is);
+                            bsdf = make_bsdf_at<EXT, DZ>(S, material, m0, is);
                         }
                     } else {
-                        bsdf = make_bsdf<EXT>(S.materials[material], is);
+                        bsdf = make_bsdf_at<EXT, DZ>(S, material, S.materials[material], is);
                     }
                     stamps.mark(2);
                     if (n_nonspec(bsdf) > 0) {  // NumComponents(BSDF_ALL & ~BSDF_SPECULAR) > 0, path.cpp:118
@@ -540,9 +547,16 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX)) void k_shade(DScene S, Pa
 void launch_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg) {
     // as many blocks as are resident at the build's waves per SIMD: the static split has no tail
     const bool tex_build = cfg.count_stats || S.textured_materials || S.probe_mode;
-    const dim3 grid(grid_blocks(max_rays, cfg.n_cus, shade_waves(tex_build)));
+    const bool dis_build = S.disney_build && !cfg.count_stats;
+    const dim3 grid(grid_blocks(max_rays, cfg.n_cus, shade_waves(tex_build, dis_build)));
     const size_t perm_bytes = S.sobol ? size_t(16) : (size_t(S.n_perms) * sizeof(uint16_t) + 15) & ~size_t(15);
-    if (S.stab_shade && !cfg.count_stats) {
+    if (dis_build) {
+        // a scene with a Disney material: the one Disney build, with the sample table or without
+        if (S.stab_shade)
+            hipLaunchKernelGGL((k_shade<false, true, true, true, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, bounce, B.queue_cap);
+        else
+            hipLaunchKernelGGL((k_shade<false, true, true, false, true>), grid, dim3(kBlock), perm_bytes, cfg.stream, S, P, B, bounce, B.queue_cap);
+    } else if (S.stab_shade && !cfg.count_stats) {
         // the scene has a sample table: the builds that read it (no permutations in LDS, no dynamic shared memory)
         if (S.textured_materials)  // (a probe pass never carries a table)
             hipLaunchKernelGGL((k_shade<false, true, true, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, bounce, B.queue_cap);

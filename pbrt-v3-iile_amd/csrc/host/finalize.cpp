@@ -125,6 +125,9 @@ bool finalize_scene(HostScene *s, std::string *err) {
     d.quadrics = s->quadrics.data();
     d.n_materials = int(s->materials.size());
     d.materials = s->materials.data();
+    s->disney.resize(s->materials.size());
+    for (const iile_material &m : s->materials)
+        if (m.type == IILE_MAT_DISNEY) d.disney = s->disney.data();   // (null in a scene without one)
     // Light::Preprocess of DistantLight (distant.cpp:63-65): Scene::WorldBound().BoundingSphere
     // (scene.h:56, geometry.h:808-811); the world bound is the BVH root's
     if (!s->nodes.empty()) {

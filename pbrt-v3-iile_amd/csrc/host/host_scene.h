@@ -35,6 +35,7 @@ struct HostScene {
     std::vector<iile_sphere> spheres;
     std::vector<iile_quadric> quadrics;  // disks and cylinders
     std::vector<iile_material> materials;
+    std::vector<iile_disney> disney;  // per material: the Disney materials' scalar parameters (iile_scene_desc::disney), zeros for the others
     std::vector<iile_light> lights;
     int n_meshes = 0;
 

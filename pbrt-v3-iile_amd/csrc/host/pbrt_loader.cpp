@@ -928,7 +928,8 @@ class Loader {
     // (an image texture stays a reference: `image_of` gets parameter name -> texture index, and the
     // parameter a placeholder colour that the material's constant-value checks see as non-black)
     // (translucent: "reflect" and "transmit" take spectrum textures as Kd .. Kt do)
-    bool resolve_textures(const ParamSet &in, ParamSet *out, std::map<std::string, int> *image_of, bool translucent = false) {
+    // (disney: "color" takes a spectrum texture)
+    bool resolve_textures(const ParamSet &in, ParamSet *out, std::map<std::string, int> *image_of, bool translucent = false, bool disney = false) {
         *out = in;
         for (Param &p : out->params) {
             if (p.type != "texture") continue;
@@ -944,9 +945,10 @@ class Loader {
             }
             if (it->second.image >= 0) {
                 const bool rt = translucent && (p.name == "reflect" || p.name == "transmit");
-                if (it->second.is_float || (p.name != "Kd" && p.name != "Ks" && p.name != "Kr" && p.name != "Kt" && p.name != "opacity" && !rt))
+                const bool dc = disney && p.name == "color";
+                if (it->second.is_float || (p.name != "Kd" && p.name != "Ks" && p.name != "Kr" && p.name != "Kt" && p.name != "opacity" && !rt && !dc))
                     return fail("image texture \"" + p.strs[0] + "\" on parameter \"" + p.name + "\" is not supported (Kd, Ks, Kr, Kt, opacity" +
-                                (translucent ? ", reflect, transmit)" : ")"));
+                                (translucent ? ", reflect, transmit)" : (disney ? ", color)" : ")")));
                 (*image_of)[p.name] = it->second.image;
                 p.strs.clear();
                 p.type = "color";  // the constant the image's value is multiplied with at the hit (1 unless "scale"d)
@@ -1002,9 +1004,46 @@ class Loader {
                     return -1;
                 }
             }
+        if (name == "disney") {  // what CreateDisneyMaterial takes and this loader does not is refused by name
+            if (const Param *p = ps_in.find("color"))
+                if (p->type == "spectrum" || p->type == "blackbody") {
+                    fail("Material \"disney\": parameter \"color\" given as \"" + p->type + "\" is not supported (rgb, color or a texture)");
+                    return -1;
+                }
+            // the ten scalar parameters: a number or a constant texture (they ride in iile_disney, one value per material)
+            for (const char *param : {"metallic", "eta", "speculartint", "anisotropic", "sheen", "sheentint", "clearcoat", "clearcoatgloss",
+                                      "spectrans", "flatness", "difftrans"}) {
+                const Param *p = ps_in.find(param);
+                if (!p || p->type != "texture" || p->strs.size() != 1) continue;
+                auto it = gs_.textures.find(p->strs[0]);
+                if (it != gs_.textures.end() && it->second.image >= 0) {
+                    fail(std::string("Material \"disney\": parameter \"") + param + "\" given as the texture \"" + p->strs[0] +
+                         "\" is not supported (a number or a constant texture)");
+                    return -1;
+                }
+            }
+            // "scatterdistance" other than black selects the BSSRDF branch (disney.cpp:515-527): a subsurface walk this renderer lacks.
+            // A thin surface never evaluates it (disney.cpp:506-513): there it is ignored, like any parameter that is not read
+            const Param *sd = ps_in.one_bool("thin", false) ? nullptr : ps_in.find("scatterdistance");
+            if (const Param *p = sd) {
+                bool black = p->type == "rgb" || p->type == "color" || p->type == "texture";
+                for (double v : p->nums) black = black && v == 0;
+                if (p->type == "texture") {
+                    auto it = p->strs.size() == 1 ? gs_.textures.find(p->strs[0]) : gs_.textures.end();
+                    black = it != gs_.textures.end() && it->second.image < 0 && it->second.v[0] == 0 && it->second.v[1] == 0 && it->second.v[2] == 0;
+                }
+                if (!black) {
+                    fail("Material \"disney\": a \"scatterdistance\" that is not black is not supported (it selects the BSSRDF, which needs a "
+                         "subsurface walk)");
+                    return -1;
+                }
+            }
+        }
         ParamSet ps;
         std::map<std::string, int> image_of;
-        if (!resolve_textures(ps_in, &ps, &image_of, name == "translucent")) return -1;
+        if (!resolve_textures(ps_in, &ps, &image_of, name == "translucent", name == "disney")) return -1;
+        iile_disney dz;
+        std::memset(&dz, 0, sizeof(dz));
         iile_material m;
         std::memset(&m, 0, sizeof(m));
         m.kd_tex = m.ks_tex = m.kr_tex = m.kt_tex = m.bump_tex = m.rough_tex = m.sigma_tex = m.opacity_tex = -1;
@@ -1125,8 +1164,28 @@ class Loader {
             m.remap_roughness = ps.one_bool("remaproughness", true) ? 1 : 0;
             // evaluated per hit in the reference (translucent.cpp:68-70); a per-material constant, so evaluated once here, as for plastic
             m.alpha = m.alpha_v = m.remap_roughness ? roughness_to_alpha(m.roughness) : m.roughness;
+        } else if (name == "disney") {  // CreateDisneyMaterial, disney.cpp:590-624
+            m.type = IILE_MAT_DISNEY;
+            float c[3] = {.5f, .5f, .5f};
+            ps.rgb("color", c);
+            for (int i = 0; i < 3; ++i) m.kd[i] = c[i];
+            m.eta = ps.one_float("eta", 1.5f);
+            // the roughness as given: DisneyMaterial squares it into the distribution's alphas at the hit and never remaps
+            m.roughness = m.roughness_v = m.alpha = m.alpha_v = ps.one_float("roughness", .5f);
+            m.remap_roughness = 0;
+            dz.metallic = ps.one_float("metallic", 0.f);
+            dz.specular_tint = ps.one_float("speculartint", 0.f);
+            dz.anisotropic = ps.one_float("anisotropic", 0.f);
+            dz.sheen = ps.one_float("sheen", 0.f);
+            dz.sheen_tint = ps.one_float("sheentint", .5f);
+            dz.clearcoat = ps.one_float("clearcoat", 0.f);
+            dz.clearcoat_gloss = ps.one_float("clearcoatgloss", 1.f);
+            dz.spec_trans = ps.one_float("spectrans", 0.f);
+            dz.flatness = ps.one_float("flatness", 0.f);
+            dz.diff_trans = ps.one_float("difftrans", 1.f);
+            dz.thin = ps.one_bool("thin", false) ? 1 : 0;
         } else {
-            fail("Material \"" + name + "\" is not supported (matte, plastic, uber, mirror, glass, metal, substrate, translucent)");
+            fail("Material \"" + name + "\" is not supported (matte, plastic, uber, mirror, glass, metal, disney, substrate, translucent)");
             return -1;
         }
         // which parameters each material looks up (an image given for one it does not have is ignored, as a
@@ -1134,6 +1193,7 @@ class Loader {
         if (m.type == IILE_MAT_MATTE || m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER || m.type == IILE_MAT_SUBSTRATE ||
             m.type == IILE_MAT_TRANSLUCENT)
             m.kd_tex = image("Kd");
+        if (m.type == IILE_MAT_DISNEY) m.kd_tex = image("color");
         if (m.type == IILE_MAT_PLASTIC || m.type == IILE_MAT_UBER || m.type == IILE_MAT_SUBSTRATE || m.type == IILE_MAT_TRANSLUCENT) m.ks_tex = image("Ks");
         if (m.type == IILE_MAT_TRANSLUCENT) m.kr_tex = image("reflect"), m.kt_tex = image("transmit");
         if (m.type == IILE_MAT_UBER || m.type == IILE_MAT_MIRROR || m.type == IILE_MAT_GLASS) m.kr_tex = image("Kr");
@@ -1153,9 +1213,9 @@ class Loader {
             const bool r_img = rp && rp->type == "roughimage", u_img = up && up->type == "roughimage", v_img = vp && vp->type == "roughimage";
             const bool uv_mat = m.type == IILE_MAT_UBER || m.type == IILE_MAT_METAL || m.type == IILE_MAT_SUBSTRATE;
             if ((r_img && m.type != IILE_MAT_PLASTIC && m.type != IILE_MAT_UBER && m.type != IILE_MAT_METAL && m.type != IILE_MAT_SUBSTRATE &&
-                 m.type != IILE_MAT_TRANSLUCENT) ||
+                 m.type != IILE_MAT_TRANSLUCENT && m.type != IILE_MAT_DISNEY) ||
                 ((u_img || v_img) && !uv_mat)) {
-                fail("roughness: a float \"imagemap\" texture is supported on plastic and translucent (\"roughness\"), uber and metal "
+                fail("roughness: a float \"imagemap\" texture is supported on plastic, translucent and disney (\"roughness\"), uber and metal "
                      "(\"roughness\", \"uroughness\", \"vroughness\") and substrate (\"uroughness\", \"vroughness\") only");
                 return -1;
             }
@@ -1172,12 +1232,14 @@ class Loader {
         }
         if (const Param *bp = ps.find("bumpmap")) {  // GetFloatTextureOrNull("bumpmap") of every material's Create*
             if (bp->type != "bumpimage" || m.type == IILE_MAT_GLASS) {
-                fail("bumpmap: only a float \"imagemap\" texture on matte / plastic / uber / mirror / metal / substrate / translucent is supported");
+                fail("bumpmap: only a float \"imagemap\" texture on matte / plastic / uber / mirror / metal / substrate / translucent / disney is supported");
                 return -1;
             }
             m.bump_tex = image("bumpmap");
         }
         scene_->materials.push_back(m);
+        scene_->disney.resize(scene_->materials.size() - 1);
+        scene_->disney.push_back(dz);
         return int(scene_->materials.size()) - 1;
     }
 
