@@ -90,7 +90,7 @@ struct HostScene {
     iile_scene_desc desc;
 };
 
-// pbrt_loader.cpp
+// pbrt_loader.cpp (with loader_textures.cpp, loader_materials.cpp, loader_lights.cpp, loader_shapes.cpp: pbrt_loader.h)
 bool load_pbrt_file(const std::string &path, HostScene *scene, std::string *err);
 // finalize.cpp: BVH build + camera + halton tables + desc
 bool finalize_scene(HostScene *scene, std::string *err);

@@ -6,7 +6,7 @@ CreateMetalMaterial (src/materials/metal.cpp:112-121) defaults "eta" and "k" to 
 CopperN / CopperK, CopperSamples). FromSampled (src/core/spectrum.h:467-488) integrates the piecewise-linear spectrum
 (InterpolateSpectrumSamples, spectrum.cpp:179-188) against the CIE matching functions (CIE_X / Y / Z at CIE_lambda,
 spectrum.cpp) and converts with XYZToRGB (spectrum.h:56-60). This script reads those tables from the given source tree, replays
-the arithmetic in float64 and writes the six results rounded to float32. The loader (pbrt_loader.cpp) carries them as constants;
+the arithmetic in float64 and writes the six results rounded to float32. The loader (loader_materials.cpp) carries them as constants;
 tests/test_metal_substrate_scenes.py checks that the two agree. Nothing of the source tree is copied: the fixture holds six numbers.
 """
 import json
