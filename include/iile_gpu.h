@@ -113,6 +113,15 @@ void iile_stream_destroy(void *stream);
 
 int iile_scene_create(const iile_scene_desc *desc, iile_scene **out);
 void iile_scene_destroy(iile_scene *scene);
+/* Gives the scene's camera its motion (iile_camera_motion, iile_scene.h; the host hands it out: iile_host_scene_camera_motion), once,
+ * before the first render: iile_camera::camera_to_world is then the transform at start_time. From here on every camera ray of
+ * iile_render and iile_render_ao — either camera, either sampler — takes dimension 2 of its camera sample as CameraSample::time and
+ * goes through AnimatedTransform::Interpolate at Lerp(time, shutter_open, shutter_close) (src/core/transform.cpp:1144-1181); the camera
+ * ray's differentials go through the same transform. A scene with a sample table gets the table's time column (one float per slot,
+ * counted against the table's byte budget: a table that no longer fits is dropped). IILE_ERR_ARG, before any device call: a null
+ * argument, a non-finite entry, end_time < start_time, a second motion. The IISPT entry points (iile_render_direct, iile_iispt_*,
+ * iile_reference_points, iile_render_probes*) refuse such a scene with IILE_ERR_UNSUPPORTED. */
+int iile_scene_set_camera_motion(iile_scene *scene, const iile_camera_motion *motion);
 
 /* film_xyzw: 4 floats per pixel of the cropped pixel bounds, row-major.
  * With tile sharding each rank's film holds its own tiles' contributions
@@ -176,6 +185,9 @@ uint64_t iile_sample_table_bytes(const iile_scene *scene);
 /* PerspectiveCamera::GenerateRayDifferential or, for an environment camera, EnvironmentCamera::GenerateRay (origin /
  * direction only). plens may be NULL; the environment camera ignores it. */
 int iile_camera_rays(iile_scene *scene, int32_t n, const float *pfilm2, const float *plens2, float *o3, float *d3);
+/* The same at ray time `time` (Ray::time itself, not a time sample: the shutter does not enter), which a moving camera alone reads;
+ * iile_camera_rays is this call at time 0. */
+int iile_camera_rays_at(iile_scene *scene, int32_t n, const float *pfilm2, const float *plens2, float time, float *o3, float *d3);
 /* Radiance of n individual camera samples through the full wavefront pipeline,
  * after the NaN / negative / inf guards; nrays (optional): {closest, shadow} per sample. */
 int iile_li_samples(iile_scene *scene, int32_t n, const int32_t *px, const int32_t *py, const int32_t *k,

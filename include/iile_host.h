@@ -118,6 +118,10 @@ int iile_host_scene_texture_level(const iile_host_scene *scene, int32_t index, i
 /* Copies the camera of a loaded scene (iile_scene_desc::camera) and returns which camera it is, IILE_CAMERA_PERSPECTIVE or
  * IILE_CAMERA_ENVIRONMENT (iile_camera_kind); -1 on a null argument. (iile_host_scene_info keeps its 15 members.) */
 int iile_host_scene_camera(const iile_host_scene *scene, iile_camera *out);
+/* The motion of the scene's camera (iile_camera_motion, iile_scene.h), for iile_scene_set_camera_motion. Non-zero, with the reason in
+ * iile_host_last_error(), for a null argument (1) or a camera that does not move (2): no `ActiveTransform` in the file, or two
+ * camera transforms that came out equal. (iile_host_scene_info keeps its 15 members.) */
+int iile_host_scene_camera_motion(const iile_host_scene *scene, iile_camera_motion *out);
 
 /* Film::filterTable of the scene's pixel filter (src/core/film.cpp:65-74): 16 x 16 floats; returns whether the
  * filter is wider than the one-pixel box (iile_scene_desc::film_filter_wide). */

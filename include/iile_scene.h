@@ -347,6 +347,22 @@ typedef struct iile_ao_params {
     int32_t cos_sample; /* "cossample" (true): CosineSampleHemisphere, else UniformSampleHemisphere */
 } iile_ao_params;
 
+/* A moving camera: the AnimatedTransform the reference gives its camera (api.cpp:1118-1123, transform.cpp:396-411) when
+ * `ActiveTransform` left the two camera-to-world transforms of the file different. Like iile_ao_params it is not part of
+ * iile_scene_desc: the host library hands it out (iile_host_scene_camera_motion, iile_host.h) and iile_scene_set_camera_motion
+ * (iile_gpu.h) takes it once per scene. iile_camera::camera_to_world is the start transform, used at and before start_time;
+ * camera_to_world_end is used at and after end_time; in between the ray goes through
+ * Translate(lerp T) * Slerp(dt, R[0], R[1]).ToTransform() * Transform(lerp S) (AnimatedTransform::Interpolate, :1144-1169).
+ * The time of a ray is Lerp(CameraSample::time, shutter_open, shutter_close) of iile_camera. */
+typedef struct iile_camera_motion {
+    float start_time, end_time;    /* `TransformTimes` (0, 1) */
+    float camera_to_world_end[16]; /* row-major, as iile_camera::camera_to_world */
+    float T[2][3];                 /* AnimatedTransform::Decompose of the start and of the end transform: translation, */
+    float R[2][4];                 /* rotation quaternion {x, y, z, w} (R[1] negated where Dot(R[0], R[1]) < 0), */
+    float S[2][16];                /* and scale, row-major: R^-1 M */
+    int32_t has_rotation;          /* Dot(R[0], R[1]) < 0.9995 (carried as the reference does; no ray reads it) */
+} iile_camera_motion;
+
 /* The IISPT probe pass: what IISPTdIntegrator::RenderView renders from a HemisphericCamera
  * (src/integrators/iispt_d.cpp:66-470, src/cameras/hemispheric.cpp:15-160): a hemi_size x hemi_size film behind a
  * Gaussian filter (radius 2, alpha 2; CreateHemisphericCamera), one Halton sample per pixel from a sampler built

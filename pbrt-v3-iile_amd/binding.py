@@ -45,6 +45,7 @@ class Camera(ctypes.Structure):
 
 
 CAMERA_PERSPECTIVE, CAMERA_ENVIRONMENT = range(2)  # IILE_CAMERA_* of include/iile_scene.h
+ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_TIMEOUT = range(1, 6)  # IILE_ERR_* of include/iile_gpu.h
 
 
 class FilmDesc(ctypes.Structure):
@@ -98,6 +99,12 @@ class AoParams(ctypes.Structure):
 
 
 INTEGRATOR_PATH, INTEGRATOR_IISPT, INTEGRATOR_AO = range(3)  # iile_host_scene_info::integrator
+
+
+class CameraMotion(ctypes.Structure):
+    """iile_camera_motion (include/iile_scene.h): a moving camera's AnimatedTransform."""
+    _fields_ = [("start_time", c_f32), ("end_time", c_f32), ("camera_to_world_end", c_f32 * 16), ("T", (c_f32 * 3) * 2),
+                ("R", (c_f32 * 4) * 2), ("S", (c_f32 * 16) * 2), ("has_rotation", c_i32)]
 
 
 class IisptTask(ctypes.Structure):
@@ -222,7 +229,7 @@ HOST_SYMBOLS = ["iile_host_load_pbrt", "iile_host_scene_desc", "iile_host_scene_
                 "iile_host_scene_texture", "iile_host_scene_texture_level", "iile_host_scene_filter_table",
                 "iile_host_sobol_matrices", "iile_host_sobol_vdc", "iile_host_write_exr", "iile_host_write_image",
                 "iile_host_scene_film_filename", "iile_host_scene_light", "iile_host_scene_quadric_count", "iile_host_scene_quadric",
-                "iile_host_scene_material", "iile_host_scene_camera", "iile_host_scene_ao"]
+                "iile_host_scene_material", "iile_host_scene_camera", "iile_host_scene_ao", "iile_host_scene_camera_motion"]
 class NetWeights(ctypes.Structure):
     """iile_iispt_net_weights (include/iile_gpu.h)."""
     _fields_ = [("conv_weight", c_vp * 15), ("conv_bias", c_vp * 15), ("bn_weight", c_vp * 5), ("bn_bias", c_vp * 5),
@@ -240,6 +247,7 @@ class DirectParams(ctypes.Structure):  # iile_direct_params
 
 
 GPU_SYMBOLS = ["iile_device_count", "iile_last_error", "iile_scene_create", "iile_scene_destroy", "iile_render",
+               "iile_scene_set_camera_motion", "iile_camera_rays_at",
                "iile_render_ao", "iile_ao_array_samples", "iile_ao_li_samples",
                "iile_trace_closest", "iile_trace_any", "iile_shape_hit_attributes", "iile_halton_samples", "iile_sample_table_records", "iile_sample_table_budget", "iile_test_sample_table_budget", "iile_sample_table_bytes", "iile_camera_rays", "iile_li_samples",
                "iile_bsdf_eval", "iile_bsdf_sample", "iile_bsdf_eval_ng", "iile_bsdf_sample_ng", "iile_bsdf_sample_specular", "iile_trig_probe", "iile_texture_eval", "iile_texture_eval_p", "iile_light_sample_li", "iile_light_sample_at", "iile_light_pdf_at", "iile_light_le", "iile_light_choose", "iile_render_probes",
@@ -282,6 +290,7 @@ def host_lib():
         lib.iile_host_scene_quadric.argtypes = [c_vp, c_i32, ctypes.POINTER(Quadric)]
         lib.iile_host_scene_material.argtypes = [c_vp, c_i32, ctypes.POINTER(Material)]
         lib.iile_host_scene_camera.argtypes = [c_vp, ctypes.POINTER(Camera)]
+        lib.iile_host_scene_camera_motion.argtypes = [c_vp, ctypes.POINTER(CameraMotion)]
         lib.iile_host_film_to_rgb.argtypes = [ctypes.POINTER(FilmDesc), c_vp, c_vp]
         lib.iile_host_write_pfm.argtypes = [ctypes.c_char_p, c_vp, c_i32, c_i32]
         lib.iile_host_read_image.argtypes = [ctypes.c_char_p, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp]
@@ -361,6 +370,8 @@ def gpu_lib():
         lib.iile_trace_any.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(GpuStats)]
         lib.iile_halton_samples.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]
         lib.iile_camera_rays.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]
+        lib.iile_camera_rays_at.argtypes = [c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]
+        lib.iile_scene_set_camera_motion.argtypes = [c_vp, ctypes.POINTER(CameraMotion)]
         lib.iile_li_samples.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         lib.iile_bsdf_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
         lib.iile_texture_eval.argtypes = [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]
@@ -568,6 +579,17 @@ class HostScene:
             raise RuntimeError(f"iile_host_scene_ao failed: {host_lib().iile_host_last_error().decode()}")
         return {"nsamples": int(p.n_samples), "cossample": bool(p.cos_sample)}
 
+    @property
+    def camera_motion(self):
+        """The CameraMotion of a scene whose camera moves (iile_host_scene_camera_motion); None for a static camera."""
+        m = CameraMotion()
+        rc = host_lib().iile_host_scene_camera_motion(self._h, ctypes.byref(m))
+        if rc == 2:  # the camera does not move
+            return None
+        if rc != 0:
+            raise RuntimeError(f"iile_host_scene_camera_motion failed: {host_lib().iile_host_last_error().decode()}")
+        return m
+
     def bvh(self):
         """(flattened nodes as a BVH_NODE array, triangle vertices (n_prims, 9) in BVH order, prim_shape (n_prims,)): copies."""
         head = ctypes.cast(self.desc, ctypes.POINTER(SceneDescHead)).contents
@@ -733,6 +755,14 @@ class GpuScene:
         rc = lib.iile_scene_create(host_scene.desc, ctypes.byref(self._s))
         if rc != 0:
             raise RuntimeError(f"iile_scene_create failed ({rc}): {lib.iile_last_error().decode()}")
+        motion = getattr(host_scene, "camera_motion", None)
+        if motion is not None:  # a moving camera travels beside the descriptor (iile_scene_set_camera_motion)
+            rc = lib.iile_scene_set_camera_motion(self._s, ctypes.byref(motion))
+            if rc != 0:
+                msg = lib.iile_last_error().decode()
+                lib.iile_scene_destroy(self._s)
+                self._s = c_vp()
+                raise RuntimeError(f"iile_scene_set_camera_motion failed ({rc}): {msg}")
 
     def _check(self, rc, what):
         if rc != 0:
@@ -871,6 +901,21 @@ class GpuScene:
         self._check(gpu_lib().iile_camera_rays(self._s, n, pfilm.ctypes.data, pl.ctypes.data if pl is not None else None,
                                                o.ctypes.data, d.ctypes.data), "iile_camera_rays")
         return o, d
+
+    def camera_rays_at(self, pfilm, time, plens=None):
+        """iile_camera_rays_at: the camera rays at ray time `time` (read by a moving camera alone)."""
+        pfilm = _f32(pfilm)
+        n = len(pfilm)
+        o = np.empty((n, 3), np.float32)
+        d = np.empty((n, 3), np.float32)
+        pl = _f32(plens) if plens is not None else None
+        self._check(gpu_lib().iile_camera_rays_at(self._s, n, pfilm.ctypes.data, pl.ctypes.data if pl is not None else None,
+                                                  c_f32(time), o.ctypes.data, d.ctypes.data), "iile_camera_rays_at")
+        return o, d
+
+    def set_camera_motion(self, motion):
+        """iile_scene_set_camera_motion with a CameraMotion (or None: the null argument); returns the call's code."""
+        return gpu_lib().iile_scene_set_camera_motion(self._s, ctypes.byref(motion) if motion is not None else None)
 
     def li_samples(self, px, py, k):
         px, py, k = _i32(px), _i32(py), _i32(k)

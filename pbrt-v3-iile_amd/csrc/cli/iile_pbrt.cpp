@@ -240,6 +240,16 @@ int main(int argc, char **argv) {
         }
         integrator_choice = IILE_INTEGRATOR_PATH;   // the same host class renders it (Scene::RenderFrame picks AOIntegrator's Li)
     }
+    {   // IISPT renders a static camera only: refused here by name, as the device calls would refuse it later
+        iile_camera_motion motion;
+        const bool iispt_frame = integrator_choice == IILE_INTEGRATOR_IISPT || (integrator_choice < 0 && scene.ok() && scene.integrator() == IILE_INTEGRATOR_IISPT);
+        if (scene.ok() && scene.camera_motion(&motion) && (reference_mode || iispt_frame)) {
+            fprintf(stderr, "iile_pbrt: %s does not go with a moving camera (ActiveTransform): the IISPT passes render a static camera only\n",
+                    reference_mode ? "--reference" : "the IISPT integrator (--integrator iispt)");
+            if (comm) iile_dist_abort(comm);
+            return 1;
+        }
+    }
     if (reference_mode) {
         if (!scene.ok()) return 1;
         if (ranked && gpus_given) {

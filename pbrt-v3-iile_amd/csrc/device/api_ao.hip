@@ -153,6 +153,7 @@ int iile_ao_li_samples(iile_scene *sc, const iile_ao_params *ao, int32_t n, cons
     P.n_paths = uint32_t(n);
     P.list_px = dx.p, P.list_py = dy.p, P.list_k = dk.p;
     LaunchCfg cfg{sc->n_cus, nullptr, true};
+    cfg.camera_moves = sc->camera_moves;
     HIP_TRY(hipMemset(sc->pb.counters, 0, sizeof(DCounters)));
     sc->pb.nray_out = dn.p;
     sc->pb.flag_count = nullptr;

@@ -125,6 +125,9 @@ struct iile_scene {
     const uint32_t *probe_pixel_offsets = nullptr;
     const float *probe_filter_table = nullptr;
     uint64_t sample_table_bytes = 0;  // HBM held by the sample table (ds.stab_*); 0: the scene has none
+    void *stab_block = nullptr;       // the table's allocation (one of `allocs`): a moving camera whose time column breaks the budget frees it
+    bool camera_moves = false;        // iile_scene_set_camera_motion gave the camera a motion (the record: camera_motion(ds), dscene.h)
+    float shutter[2] = {0.f, 1.f};    // iile_camera::shutter_open / shutter_close, for iile_scene_set_camera_motion
     uint32_t *flag_count = nullptr;  // whole-number film positions (PassBuffers::flag_count / flag_rec)
     float *flag_rec = nullptr;
     iile::DevBlock probe_block;  // cameras + aux + outputs of the last probe batch

@@ -10,8 +10,15 @@ using namespace iile;
 
 extern "C" {
 // ---- IISPT direct pass (kernels_direct.hip) -------------------------------------
+// IISPT is built around one camera — the probe gather makes "the" main camera ray (iispt.hip), the reference's reference mode fixes
+// time = 0 — so every entry point of it refuses a scene whose camera moves, before any launch
+static int refuse_moving_camera(const char *who) {
+    return api_fail(IILE_ERR_UNSUPPORTED, std::string(who) + ": the scene has a moving camera (iile_scene_set_camera_motion); the IISPT passes render a static camera only");
+}
+
 int iile_render_direct(iile_scene *sc, const iile_direct_params *prm, double *film_rgbw) {
     if (!sc || !prm || !film_rgbw || prm->n_passes < 0 || prm->first_pass < 0) return api_fail(IILE_ERR_ARG, "iile_render_direct: bad argument");
+    if (sc->camera_moves) return refuse_moving_camera("iile_render_direct");
     int rc = ensure_device();
     if (rc) return rc;
     DScene S = sc->ds;
@@ -260,6 +267,7 @@ int iile_render_probes(iile_scene *sc, int32_t n_probes, const float *pos3, cons
                        float *distance, int32_t outputs_on_device, iile_stats *stats, void *stream_arg) {
     if (!sc || n_probes < 0 || !pos3 || !dir3 || !intensity_rgb || !normals_xyz || !distance)
         return api_fail(IILE_ERR_ARG, "iile_render_probes: null argument");
+    if (sc->camera_moves) return refuse_moving_camera("iile_render_probes");
     int rc = ensure_device();
     if (rc) return rc;
     const iile_probe_setup &pr = sc->probe;
@@ -362,6 +370,7 @@ int iile_render_probes(iile_scene *sc, int32_t n_probes, const float *pos3, cons
 int iile_render_probes_reference(iile_scene *sc, int32_t n_probes, const float *pos3, const float *dir3, const iile_probe_ref_params *prm,
                                  float *intensity_rgb, float *weight_sum, float *normals_xyz, float *distance, iile_stats *stats) {
     if (!sc || n_probes < 0 || !pos3 || !dir3 || !prm || !intensity_rgb) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: null argument");
+    if (sc->camera_moves) return refuse_moving_camera("iile_render_probes_reference");
     if (prm->n_samples < 1) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: n_samples < 1");
     if (prm->first_sample < 0) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: first_sample < 0");
     if (prm->max_depth < 1 || prm->max_depth > 14) return api_fail(IILE_ERR_ARG, "iile_render_probes_reference: max_depth outside 1 .. 14");
@@ -499,6 +508,7 @@ int iile_test_probe_ref_group(iile_scene *sc, uint32_t samples_per_group) {
 
 int iile_reference_points(iile_scene *sc, int32_t n, const float *pfilm2, uint8_t *valid, float *pos3, float *dir3) {
     if (!sc || n < 0 || !pfilm2 || !valid || !pos3 || !dir3) return api_fail(IILE_ERR_ARG, "iile_reference_points: bad argument");
+    if (sc->camera_moves) return refuse_moving_camera("iile_reference_points");
     int rc = ensure_device();
     if (rc) return rc;
     if (n == 0) return IILE_OK;
@@ -708,6 +718,7 @@ int gather_slice(iile_scene *sc, const iile_iispt_task *tasks, int n_tasks, cons
 
 int iile_iispt_hemi_points_batch(iile_scene *sc, const iile_iispt_task *tasks, int32_t n_tasks, uint8_t *valid, float *pos3, float *dir3, void *stream) {
     if (!sc || !tasks || n_tasks < 1) return api_fail(IILE_ERR_ARG, "iile_iispt_hemi_points: no task");
+    if (sc->camera_moves) return refuse_moving_camera("iile_iispt_hemi_points");
     if (!valid || !pos3 || !dir3) return api_fail(IILE_ERR_ARG, "iile_iispt_hemi_points: null output");
     size_t first = 0;
     const int slice = iispt_slice_jobs(sc);
@@ -727,6 +738,7 @@ int iile_iispt_hemi_points(iile_scene *sc, const iile_iispt_task *t, uint8_t *va
 int iile_iispt_gather_batch(iile_scene *sc, const iile_iispt_task *tasks, int32_t n_tasks, const uint8_t *valid, const float *pos3, const float *dir3,
                             const float *nn_films, int32_t nn_on_device, float *out_rgbw, int32_t out_on_device, void *stream) {
     if (!sc || !tasks || n_tasks < 1) return api_fail(IILE_ERR_ARG, "iile_iispt_gather: no task");
+    if (sc->camera_moves) return refuse_moving_camera("iile_iispt_gather");
     if (!valid || !pos3 || !dir3 || !nn_films || !out_rgbw) return api_fail(IILE_ERR_ARG, "iile_iispt_gather: null argument");
     const size_t per_hemi = size_t(sc->probe.hemi_size) * sc->probe.hemi_size * 3;
     size_t first_h = 0, first_p = 0;
@@ -747,6 +759,7 @@ int iile_iispt_film_add(iile_scene *sc, const iile_iispt_task *tasks, int32_t n_
                         int32_t film_w, int32_t film_h, void *stream) {
     if (!sc || !tasks || n_tasks < 1 || !out_rgbw_dev || !film_rgbw_dev || film_w < 1 || film_h < 1)
         return api_fail(IILE_ERR_ARG, "iile_iispt_film_add: bad argument");
+    if (sc->camera_moves) return refuse_moving_camera("iile_iispt_film_add");
     if (n_tasks > 65535) return api_fail(IILE_ERR_UNSUPPORTED, "iile_iispt_film_add: more than 65535 tasks in one call");
     std::vector<int4> rects(static_cast<size_t>(n_tasks));
     std::vector<uint32_t> first(static_cast<size_t>(n_tasks));

@@ -8,7 +8,11 @@
 using namespace iile;
 
 namespace {
-LaunchCfg probe_cfg(const iile_scene *sc, bool count_stats = false) { return LaunchCfg{sc->n_cus, nullptr, count_stats}; }
+LaunchCfg probe_cfg(const iile_scene *sc, bool count_stats = false) {
+    LaunchCfg cfg{sc->n_cus, nullptr, count_stats};
+    cfg.camera_moves = sc->camera_moves;
+    return cfg;
+}
 // The tail of every entry point here: the launch's error, the device drained, the (first) result downloaded.
 template <typename T>
 int finish(DevBuf<T> &dev, T *host, size_t n) {
@@ -133,13 +137,18 @@ uint64_t iile_sample_table_bytes(const iile_scene *sc) { return sc ? sc->sample_
 
 int iile_camera_rays(iile_scene *sc, int32_t n, const float *pfilm2, const float *plens2, float *o3, float *d3) {
     if (!sc || n < 0 || !pfilm2 || !o3 || !d3) return api_fail(IILE_ERR_ARG, "iile_camera_rays: bad argument");
+    return iile_camera_rays_at(sc, n, pfilm2, plens2, 0.f, o3, d3);
+}
+int iile_camera_rays_at(iile_scene *sc, int32_t n, const float *pfilm2, const float *plens2, float time, float *o3, float *d3) {
+    if (!sc || n < 0 || !pfilm2 || !o3 || !d3) return api_fail(IILE_ERR_ARG, "iile_camera_rays_at: bad argument");
+    if (!(time == time)) return api_fail(IILE_ERR_ARG, "iile_camera_rays_at: the time is not a number");
     int rc = ensure_device();
     if (rc) return rc;
     DevBuf<float> df, dl, dox, ddx;
     if ((rc = df.put(pfilm2, 2 * size_t(n))) || (rc = dox.alloc(3 * size_t(n))) || (rc = ddx.alloc(3 * size_t(n))))
         return rc;
     if (plens2 && (rc = dl.put(plens2, 2 * size_t(n)))) return rc;
-    if (n) launch_camera(sc->ds, n, df.p, plens2 ? dl.p : nullptr, dox.p, ddx.p, probe_cfg(sc));
+    if (n) launch_camera(sc->ds, n, df.p, plens2 ? dl.p : nullptr, time, dox.p, ddx.p, probe_cfg(sc));
     if ((rc = finish(dox, o3, 3 * size_t(n))) || (rc = ddx.get(d3, 3 * size_t(n)))) return rc;
     return IILE_OK;
 }

@@ -266,7 +266,7 @@ int run_pass(iile_scene *sc, const DScene &S_in, int max_depth, const PassDesc &
     if (cfg.count_stats || P.list_px || S.probe_mode || P.k0 < 0 || uint64_t(P.k0) + uint64_t(P.kc) > uint64_t(S.stab_spp) || max_depth > S.max_depth)
         clear_sample_table(&S);
     // camera rays made inside the first extend / shade (see PassDesc::gen_fused) where nothing else reads queue 0
-    P.gen_fused = !cfg.count_stats && !P.list_px && !S.has_infinite && !S.probe_mode && !B.nray_out && !S.env_camera;  // (camera_ray<false>)
+    P.gen_fused = !cfg.count_stats && !P.list_px && !S.has_infinite && !S.probe_mode && !B.nray_out && !S.env_camera && !cfg.camera_moves;  // (camera_ray<false>)
     HIP_TRY(hipMemsetAsync(B.counts, 0, kCntWords * sizeof(uint32_t), cfg.stream));
     auto timed_launch_on = [&](hipStream_t stream, int kind, auto &&fn) -> int { return timed_step(sc, timed, stream, kind, fn); };
     auto timed_launch = [&](int kind, auto &&fn) -> int { return timed_launch_on(cfg.stream, kind, fn); };
@@ -358,6 +358,7 @@ int render_frame(iile_scene *sc, const iile_render_params *prm, float *film_xyzw
     if (rank < 0 || rank >= nranks) return api_fail(IILE_ERR_ARG, "iile_render: tile_rank out of range");
     hipStream_t stream = static_cast<hipStream_t>(prm->stream);
     LaunchCfg cfg{sc->n_cus, stream, prm->collect_stats != 0};
+    cfg.camera_moves = sc->camera_moves;
     const bool timed = prm->time_kernels != 0;
 
     PassDesc P;
@@ -543,6 +544,7 @@ int iile_li_samples(iile_scene *sc, int32_t n, const int32_t *px, const int32_t 
     P.n_paths = uint32_t(n);
     P.list_px = dx.p, P.list_py = dy.p, P.list_k = dk.p;
     LaunchCfg cfg{sc->n_cus, nullptr, true};
+    cfg.camera_moves = sc->camera_moves;
     HIP_TRY(hipMemset(sc->pb.counters, 0, sizeof(DCounters)));
     sc->pb.nray_out = dn.p;
     sc->events_used = 0;

@@ -4,6 +4,7 @@
 #include <array>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -590,7 +591,8 @@ int build_lights(iile_scene *sc, const iile_scene_desc &d) {
 // HaltonSampler::GetIndexForSample's per-pixel offset (halton.cpp:96-122) depends only on the pixel modulo
 // kMaxResolution = 128: tabulated once (integer arithmetic, exact)
 std::vector<uint32_t> halton_pixel_offsets(const int32_t *scales, const int32_t *exps, int32_t stride, const int32_t *mult_inv) {
-    std::vector<uint32_t> offs(128 * 128, 0u);
+    static_assert(kPixelOffsets == 128 * 128, "camera_motion (dscene.h) lies behind exactly these offsets");
+    std::vector<uint32_t> offs(kPixelOffsets, 0u);
     if (stride <= 1) return offs;
     for (int pmy = 0; pmy < 128; ++pmy)
         for (int pmx = 0; pmx < 128; ++pmx) {
@@ -635,7 +637,8 @@ int build_halton(iile_scene *sc, const iile_scene_desc &d) {
     S.base_scale0 = h.base_scales[0], S.base_scale1 = h.base_scales[1], S.base_exp0 = h.base_exponents[0], S.base_exp1 = h.base_exponents[1];
     S.mult_inv0 = h.mult_inverse[0], S.mult_inv1 = h.mult_inverse[1];
     sc->spp = h.spp;
-    const std::vector<uint32_t> offs = halton_pixel_offsets(h.base_scales, h.base_exponents, h.sample_stride, h.mult_inverse);
+    std::vector<uint32_t> offs = halton_pixel_offsets(h.base_scales, h.base_exponents, h.sample_stride, h.mult_inverse);
+    offs.resize(size_t(kPixelOffsets) + (sizeof(DCameraMotion) + 3) / 4, 0u);  // room for a moving camera's record (camera_motion, dscene.h)
     sc->probe = d.probe;
     if (d.probe.hemi_size > 0 && d.probe.sample_stride > 0) {
         const std::vector<uint32_t> poffs =
@@ -707,6 +710,7 @@ int build_camera_film(iile_scene *sc, const iile_scene_desc &d) {
     S.filter_rx = f.filter_rx, S.filter_ry = f.filter_ry, S.max_sample_luminance = f.max_sample_luminance;
     S.max_depth = d.integrator.max_depth, S.rr_threshold = d.integrator.rr_threshold;
     sc->max_depth = d.integrator.max_depth;
+    sc->shutter[0] = d.camera.shutter_open, sc->shutter[1] = d.camera.shutter_close;
     return IILE_OK;
 }
 
@@ -801,6 +805,7 @@ int build_sample_table(iile_scene *sc, const iile_scene_desc &d) {
     if (S.sobol || S.max_depth <= 0 || spp <= 0 || S.sample_stride <= 0 || std::getenv("IILE_NO_SAMPLE_TABLE")) return IILE_OK;
     if (5 + 7 * int64_t(S.max_depth) >= int64_t(S.n_hdims)) return IILE_OK;  // the last record's last dimension: 12 + 7 (maxdepth - 1)
     const bool lens = S.lens_radius > 0;
+    // (a moving camera's time column, 4 bytes a slot more, is counted when the motion arrives: iile_scene_set_camera_motion)
     const uint64_t per_slot = uint64_t(32) * uint64_t(S.max_depth) + (lens ? 16 : 8);
     if (uint64_t(spp) > sample_table_budget() / (uint64_t(16384) * per_slot)) return IILE_OK;
     const uint64_t slots = uint64_t(16384) * uint64_t(spp);  // (< 2^32: the budget is far below 2^32 slots of 40 bytes or more)
@@ -831,6 +836,7 @@ int build_sample_table(iile_scene *sc, const iile_scene_desc &d) {
         return IILE_OK;
     }
     sc->allocs.push_back(block);
+    sc->stab_block = block;
     layout(Carver(block));
     launch_sample_table(S, cam, lens_part, shade, LaunchCfg{sc->n_cus, nullptr, false});
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return api_fail(IILE_ERR_HIP, "sample table kernel failed");
@@ -961,6 +967,65 @@ int iile_scene_create(const iile_scene_desc *d, iile_scene **out) {
         }
     }
     *out = sc;
+    return IILE_OK;
+}
+
+// The camera of the scene moves from now on (iile_camera_motion, iile_scene.h): every camera ray of iile_render, iile_render_ao and
+// the kernel-level probes goes through the transform interpolated at its own time. Checked first, without a device call; then
+// one record goes to HBM and, where the scene has a sample table, the table's time column — unless the table with that column no
+// longer fits its byte budget, or the device has no room for the column: the scene then gives the table up and renders by the
+// digit chains.
+int iile_scene_set_camera_motion(iile_scene *sc, const iile_camera_motion *mo) {
+    if (!sc || !mo) return api_fail(IILE_ERR_ARG, "iile_scene_set_camera_motion: null argument");
+    if (sc->camera_moves) return api_fail(IILE_ERR_ARG, "iile_scene_set_camera_motion: the scene's camera has a motion already");
+    auto finite = [](const float *v, size_t n) {
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(v[i])) return false;
+        return true;
+    };
+    if (!finite(&mo->start_time, 1) || !finite(&mo->end_time, 1) || !finite(mo->camera_to_world_end, 16) || !finite(&mo->T[0][0], 6) ||
+        !finite(&mo->R[0][0], 8) || !finite(&mo->S[0][0], 32))
+        return api_fail(IILE_ERR_ARG, "iile_scene_set_camera_motion: a non-finite entry in the camera motion");
+    if (mo->end_time < mo->start_time) return api_fail(IILE_ERR_ARG, "iile_scene_set_camera_motion: the motion ends before it starts (TransformTimes)");
+    int rc = ensure_device();
+    if (rc) return rc;
+    DScene &S = sc->ds;
+    DCameraMotion dm;
+    std::memset(&dm, 0, sizeof(dm));
+    dm.c2w_start = S.camera_to_world;
+    std::memcpy(dm.c2w_end.m, mo->camera_to_world_end, 64);
+    dm.start_time = mo->start_time, dm.end_time = mo->end_time;
+    dm.shutter_open = sc->shutter[0], dm.shutter_close = sc->shutter[1];
+    std::memcpy(dm.T, mo->T, sizeof(dm.T));
+    std::memcpy(dm.R, mo->R, sizeof(dm.R));
+    for (int k = 0; k < 2; ++k)
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) dm.S[k][3 * i + j] = mo->S[k][4 * i + j];
+    if (S.stab_cam) {
+        const uint64_t slots = S.stab_slots;
+        void *time = nullptr;
+        if (sc->sample_table_bytes + 4 * slots <= sample_table_budget() && hipMalloc(&time, size_t(slots) * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();  // (the failure is answered here)
+            time = nullptr;
+        }
+        if (!time) {
+            // over the budget with its time column, or no room on the device for it: no table (build_sample_table's rules)
+            for (void *&p : sc->allocs)
+                if (p == sc->stab_block) p = nullptr;
+            HIP_TRY(hipFree(sc->stab_block));
+            sc->stab_block = nullptr;
+            clear_sample_table(&S);
+            sc->sample_table_bytes = 0;
+        } else {
+            sc->allocs.push_back(time);
+            launch_sample_table_time(S, static_cast<float *>(time), LaunchCfg{sc->n_cus, nullptr, false});  // (reads no motion record)
+            if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return api_fail(IILE_ERR_HIP, "sample table time kernel failed");
+            dm.stab_time = static_cast<float *>(time);
+            sc->sample_table_bytes += 4 * slots;
+        }
+    }
+    HIP_TRY(hipMemcpy(const_cast<DCameraMotion *>(camera_motion(S)), &dm, sizeof(dm), hipMemcpyHostToDevice));
+    sc->camera_moves = true;
     return IILE_OK;
 }
 

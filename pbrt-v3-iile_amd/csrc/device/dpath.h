@@ -308,12 +308,74 @@ static __device__ __attribute__((noinline)) F3 env_camera_direction(float pfx, f
     sincos_f(phi, &sp, &cp);
     return F3{st * cp, ct, st * sp};
 }
+// A moving camera's CameraToWorld at `time` (AnimatedTransform::Interpolate, transform.cpp:1144-1169, with Slerp and
+// Quaternion::ToTransform, quaternion.cpp:41-59, 94-104): the stored start transform at or before the start time, the stored end
+// transform at or after the end time — so a closed shutter is a static camera, bit for bit — and otherwise
+// Translate(lerp T) * Slerp(dt, R0, R1).ToTransform() * Transform(lerp S), both products as Matrix4x4::Mul forms them. A call, like
+// env_camera_direction and for its reason: whether the camera moves is a scene constant, and inline this branch would change the
+// registers of every kernel that makes a camera ray for a camera that stands still. It gets the record's address and not the
+// scene, which a kernel holds in registers.
+static __device__ __attribute__((noinline)) M44 camera_to_world_motion(const DCameraMotion *mo, float time) {
+    if (time <= mo->start_time) return mo->c2w_start;
+    if (time >= mo->end_time) return mo->c2w_end;
+    const float dt = (time - mo->start_time) / (mo->end_time - mo->start_time);
+    const float *T0 = mo->T[0], *T1 = mo->T[1], *q1 = mo->R[0], *q2 = mo->R[1];
+    const float tx = (1 - dt) * T0[0] + dt * T1[0], ty = (1 - dt) * T0[1] + dt * T1[1], tz = (1 - dt) * T0[2] + dt * T1[2];
+    // Slerp(dt, R[0], R[1])
+    float q[4];
+    const float cos_theta = (q1[0] * q2[0] + q1[1] * q2[1] + q1[2] * q2[2]) + q1[3] * q2[3];
+    if (cos_theta > .9995f) {
+        for (int i = 0; i < 4; ++i) q[i] = (1 - dt) * q1[i] + dt * q2[i];
+        const float len = sqrtf((q[0] * q[0] + q[1] * q[1] + q[2] * q[2]) + q[3] * q[3]), inv = 1.f / len;
+        q[0] *= inv, q[1] *= inv, q[2] *= inv, q[3] = q[3] / len;  // Normalize: v /= f multiplies by the reciprocal, w /= f divides
+    } else {
+        const float theta = acos_f(mn(mx(cos_theta, -1.f), 1.f));
+        const float thetap = theta * dt;
+        float qp[4];
+        for (int i = 0; i < 4; ++i) qp[i] = q2[i] - q1[i] * cos_theta;
+        const float len = sqrtf((qp[0] * qp[0] + qp[1] * qp[1] + qp[2] * qp[2]) + qp[3] * qp[3]), inv = 1.f / len;
+        qp[0] *= inv, qp[1] *= inv, qp[2] *= inv, qp[3] = qp[3] / len;
+        float st, ct;
+        sincos_f(thetap, &st, &ct);
+        for (int i = 0; i < 4; ++i) q[i] = q1[i] * ct + qp[i] * st;
+    }
+    // rotate.ToTransform().m: the transpose of the matrix the quaternion spells out
+    const float xx = q[0] * q[0], yy = q[1] * q[1], zz = q[2] * q[2];
+    const float xy = q[0] * q[1], xz = q[0] * q[2], yz = q[1] * q[2];
+    const float wx = q[0] * q[3], wy = q[1] * q[3], wz = q[2] * q[3];
+    float R[16] = {1 - 2 * (yy + zz), 2 * (xy - wz), 2 * (xz + wy), 0,
+                   2 * (xy + wz), 1 - 2 * (xx + zz), 2 * (yz - wx), 0,
+                   2 * (xz - wy), 2 * (yz + wx), 1 - 2 * (xx + yy), 0,
+                   0, 0, 0, 1};
+    float Tm[16] = {1, 0, 0, tx, 0, 1, 0, ty, 0, 0, 1, tz, 0, 0, 0, 1};
+    float Sm[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Sm[4 * i + j] = (1 - dt) * mo->S[0][3 * i + j] + dt * mo->S[1][3 * i + j];
+    float TR[16];
+    M44 out;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j)
+            TR[4 * i + j] = Tm[4 * i] * R[j] + Tm[4 * i + 1] * R[4 + j] + Tm[4 * i + 2] * R[8 + j] + Tm[4 * i + 3] * R[12 + j];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j)
+            out.m[4 * i + j] = TR[4 * i] * Sm[j] + TR[4 * i + 1] * Sm[4 + j] + TR[4 * i + 2] * Sm[8 + j] + TR[4 * i + 3] * Sm[12 + j];
+    return out;
+}
+DEV M44 camera_to_world_at(const DScene &S, float time) { return camera_to_world_motion(camera_motion(S), time); }
+// ray.time = Lerp(CameraSample::time, shutterOpen, shutterClose) (perspective.cpp:117, environment.cpp:52), in a moving camera's builds
+DEV float camera_ray_time(const DScene &S, float u_time) {
+    const DCameraMotion *mo = camera_motion(S);
+    return (1 - u_time) * mo->shutter_open + u_time * mo->shutter_close;
+}
 // ANY_CAMERA = false: the perspective camera alone, for the two sites that make their camera ray inside a persistent traversal /
-// shading loop (PassDesc::gen_fused, which a pass with an environment camera does not set): with the other camera's branch in
-// them, k_extend<.., GEN> and the plain k_shade take more scratch, whichever way that branch is compiled.
-template <bool ANY_CAMERA = true>
+// shading loop (PassDesc::gen_fused, which a pass with an environment camera or a moving one does not set): with the other
+// camera's branch in them, k_extend<.., GEN> and the plain k_shade take more scratch, whichever way that branch is compiled.
+// MOVING = true: the kernel builds of a moving camera (LaunchCfg::camera_moves; k_generate<true>, k_camera_at, k_shade<.., MOT>), which
+// send the ray through the transform at `time` (camera_ray_time). Every other build has none of that code and is, instruction for
+// instruction, what it was before cameras moved.
+template <bool ANY_CAMERA = true, bool MOVING = false>
 DEV void camera_ray(const DScene &S, float pfx, float pfy, float lu0, float lu1, F3 *o_out, F3 *d_out, float *tmax,
-                    const float zero = 0.f) {
+                    const float zero = 0.f, const float time = 0.f) {
     F3 ro = F3{zero, zero, zero};
     F3 rd;
     if (ANY_CAMERA && S.env_camera) {
@@ -334,9 +396,15 @@ DEV void camera_ray(const DScene &S, float pfx, float pfy, float lu0, float lu1,
             rd = normalize(pfocus - ro);
         }
     }
-    F3 oerr;
-    F3 o = xf_point_err(S.camera_to_world, ro, &oerr);
-    F3 d = xf_vector(S.camera_to_world, rd);
+    F3 oerr, o, d;
+    if (MOVING) {  // CameraToWorld(ray) of an AnimatedTransform, transform.cpp:1171-1181
+        const M44 c2w = camera_to_world_at(S, time);
+        o = xf_point_err(c2w, ro, &oerr);
+        d = xf_vector(c2w, rd);
+    } else {
+        o = xf_point_err(S.camera_to_world, ro, &oerr);
+        d = xf_vector(S.camera_to_world, rd);
+    }
     float len2 = length_sq(d);
     float tm = IILE_INF;
     if (len2 > 0) {
@@ -381,12 +449,14 @@ struct RayDiff {
 // The environment camera has no GenerateRayDifferential of its own: Camera::GenerateRayDifferential (camera.cpp:60-96), the
 // rays through the film points shifted by eps = 0.05 in x and in y, differenced (every ray's weight is 1, so the -0.05 retry
 // never runs); then ScaleDifferentials
-DEV RayDiff env_camera_differentials(const DScene &S, float pfx, float pfy, F3 o, F3 d) {
+// (the two shifted rays are made from the same CameraSample, so at the same time)
+template <bool MOVING>
+DEV RayDiff env_camera_differentials(const DScene &S, float pfx, float pfy, F3 o, F3 d, float time) {
     const float eps = .05f;
     F3 xo, xd, yo, yd;
     float tm;
-    camera_ray(S, pfx + eps, pfy, 0.f, 0.f, &xo, &xd, &tm);
-    camera_ray(S, pfx, pfy + eps, 0.f, 0.f, &yo, &yd, &tm);
+    camera_ray<true, MOVING>(S, pfx + eps, pfy, 0.f, 0.f, &xo, &xd, &tm, 0.f, time);
+    camera_ray<true, MOVING>(S, pfx, pfy + eps, 0.f, 0.f, &yo, &yd, &tm, 0.f, time);
     const float inv = 1.f / eps;  // Vector3::operator/ multiplies by the reciprocal
     const F3 rxo = o + (xo - o) * inv, rxd = d + (xd - d) * inv;
     const F3 ryo = o + (yo - o) * inv, ryd = d + (yd - d) * inv;
@@ -398,8 +468,11 @@ DEV RayDiff env_camera_differentials(const DScene &S, float pfx, float pfy, F3 o
     r.ryd = d + (ryd - d) * sc;
     return r;
 }
-DEV RayDiff camera_differentials(const DScene &S, float pfx, float pfy, float lu0, float lu1, F3 o, F3 d) {
-    if (S.env_camera) return env_camera_differentials(S, pfx, pfy, o, d);
+// MOVING (a moving camera's builds, as camera_ray): `time` is the camera ray's own, and the auxiliary rays go through the same
+// interpolated transform (AnimatedTransform::operator()(RayDifferential), transform.cpp:1183-1193)
+template <bool MOVING = false>
+DEV RayDiff camera_differentials(const DScene &S, float pfx, float pfy, float lu0, float lu1, F3 o, F3 d, float time = 0.f) {
+    if (S.env_camera) return env_camera_differentials<MOVING>(S, pfx, pfy, o, d, time);
     const F3 pcam = xf_point(S.raster_to_camera, F3{pfx, pfy, 0});
     const F3 dxc = F3{S.dx_camera[0], S.dx_camera[1], S.dx_camera[2]}, dyc = F3{S.dy_camera[0], S.dy_camera[1], S.dy_camera[2]};
     F3 rxo = F3{0, 0, 0}, ryo = F3{0, 0, 0}, rxd, ryd;
@@ -422,10 +495,18 @@ DEV RayDiff camera_differentials(const DScene &S, float pfx, float pfy, float lu
         rxd = normalize(pcam + dxc);
         ryd = normalize(pcam + dyc);
     }
-    rxo = xf_point(S.camera_to_world, rxo);
-    ryo = xf_point(S.camera_to_world, ryo);
-    rxd = xf_vector(S.camera_to_world, rxd);
-    ryd = xf_vector(S.camera_to_world, ryd);
+    if (MOVING) {
+        const M44 c2w = camera_to_world_at(S, time);
+        rxo = xf_point(c2w, rxo);
+        ryo = xf_point(c2w, ryo);
+        rxd = xf_vector(c2w, rxd);
+        ryd = xf_vector(c2w, ryd);
+    } else {
+        rxo = xf_point(S.camera_to_world, rxo);
+        ryo = xf_point(S.camera_to_world, ryo);
+        rxd = xf_vector(S.camera_to_world, rxd);
+        ryd = xf_vector(S.camera_to_world, ryd);
+    }
     const float sc = S.diff_scale;
     RayDiff r;
     r.rxo = o + (rxo - o) * sc;

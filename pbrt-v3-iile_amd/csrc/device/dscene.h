@@ -134,6 +134,20 @@ constexpr int kMaxTop = IILE_TOP_RECORDS;  // records of the tree's top kept in 
 constexpr int kRefShift = 2;
 constexpr int kTopFlag = 1 << 28;  // reference to a record of the LDS top: kTopFlag | slot (survives the shift)
 
+// A moving camera (iile_camera_motion; AnimatedTransform, transform.cpp:396-411, 1144-1169): one record in HBM right behind the
+// DScene::pixel_offsets table (camera_motion below), as the Disney table lies behind the materials. DScene has no member for it
+// and keeps its size: the kernels take it by value, and eight bytes more moved the scratch of kernels that never read them.
+// Whether the camera moves is no scene constant on the device either: the launchers know (LaunchCfg::camera_moves) and pick
+// the kernel builds that read the record. The start transform is DScene::camera_to_world once more: camera_to_world_at is a
+// call, and gets this record's address alone.
+struct DCameraMotion {
+    M44 c2w_start, c2w_end;
+    float start_time, end_time;         // `TransformTimes`
+    float shutter_open, shutter_close;  // ray.time = Lerp(CameraSample::time, shutterOpen, shutterClose)
+    float T[2][3], R[2][4], S[2][9];    // Decompose of both: translation, quaternion {x, y, z, w}, the scale's upper 3 x 3
+    const float *stab_time;             // [slot] dimension 2 of the sample table (DScene::stab_*), or null where the scene has none
+};
+
 struct DScene {
     // HBM arrays
     const float4 *wide;       // 4 float4 per interior node: both child boxes + child refs + split axis
@@ -226,6 +240,11 @@ struct DScene {
     float rr_threshold;
 };
 static_assert(sizeof(DScene) == 672, "DScene keeps its size: the kernels take it by value, and their register allocation follows its layout");
+// the moving camera's record (room for it lies behind every scene's pixel_offsets; filled by iile_scene_set_camera_motion)
+constexpr int kPixelOffsets = 128 * 128;
+inline __host__ __device__ const DCameraMotion *camera_motion(const DScene &S) {
+    return reinterpret_cast<const DCameraMotion *>(S.pixel_offsets + kPixelOffsets);
+}
 // the Disney materials' scalar parameters, entry for entry with the materials (only in a scene that has a Disney material)
 inline __host__ __device__ const iile_disney *disney_table(const DScene &S) {
     return reinterpret_cast<const iile_disney *>(S.materials + S.n_materials);

@@ -121,6 +121,7 @@ struct LaunchCfg {
     hipStream_t stream;
     bool count_stats;
     int trav_blocks_per_cu = 0;   // persistent traversal blocks per CU; 0 = default_trav_blocks_per_cu()
+    bool camera_moves = false;    // the scene's camera has a motion (iile_scene::camera_moves): the launchers pick the builds that read it
 };
 
 // api_scene.hip: records the message iile_last_error() returns, hands back `code`
@@ -139,6 +140,8 @@ uint32_t queue_capacity(uint32_t n_paths, int n_cus);
 void launch_generate(const DScene &S, const PassDesc &P, const PassBuffers &B, const LaunchCfg &cfg);
 void launch_extend(const DScene &S, const PassDesc &P, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
 void launch_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
+// kernels_shade_motion.hip: k_shade's builds for a moving camera over textured materials (launch_shade hands over to it)
+void launch_shade_motion(const DScene &S, const PassDesc &P, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
 void launch_shadow(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
 void launch_mis(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
 // the spatial light distribution's table: 2 n + 2 floats per voxel of S.light_nv (k_light_contrib, then k_light_cdf)
@@ -146,6 +149,7 @@ void launch_light_distributions(const DScene &S, const float *samples, float *ou
 // the sample table (DScene::stab_*): S carries its geometry (stab_slots, stab_spp and the divider); cam / lens (may be null) /
 // shade are filled by the digit chains. launch_sample_table_read: the test probe's reader (8 floats per query)
 void launch_sample_table(const DScene &S, float2 *cam, float2 *lens, float4 *shade, const LaunchCfg &cfg);
+void launch_sample_table_time(const DScene &S, float *time, const LaunchCfg &cfg);  // the time column of a moving camera's table
 void launch_sample_table_read(const DScene &S, int n, const int *px, const int *py, const int *k, const int *bounce, float *out, const LaunchCfg &cfg);
 void launch_miss(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
 void launch_mis_lit(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg);
@@ -249,7 +253,7 @@ int default_trav_blocks_per_cu();
 // ---- kernel-level probes of single device functions (kernels_probes.hip) ----
 void launch_halton(const DScene &S, int n, const int *px, const int *py, const int *k, int dim0, int ndims,
                    float *out, uint32_t *index_out, const LaunchCfg &cfg);
-void launch_camera(const DScene &S, int n, const float *pfilm, const float *plens, float *o, float *d,
+void launch_camera(const DScene &S, int n, const float *pfilm, const float *plens, float time, float *o, float *d,
                    const LaunchCfg &cfg);
 void launch_bsdf_probe(const DScene &S, int n, int mat, const float *wo, const float *wi_or_u, int sample,
                        float *out, const float ng[3], const LaunchCfg &cfg);

@@ -22,6 +22,8 @@
 namespace iile {
 
 // ---------------------------------------------------------------------------
+// MOT: the build for a moving camera (camera_motion, dscene.h): dimension 2 of the camera sample is the ray's time
+template <bool MOT>
 __global__ __launch_bounds__(kBlock) void k_generate(DScene S, PassDesc P, PassBuffers B, int count_stats) {
     unsigned long long n_cam = 0;
     for (uint32_t base = blockIdx.x * kBlock; base < P.n_paths; base += gridDim.x * kBlock) {
@@ -36,7 +38,8 @@ __global__ __launch_bounds__(kBlock) void k_generate(DScene S, PassDesc P, PassB
             // Sampler::GetCameraSample (sampler.cpp:46-52): dims 0,1 film, 2 time, 3,4 lens
             // (with a sample table — DScene::stab_cam — read from it; idx is then the sample's slot, as the table build of k_shade wants)
             uint32_t idx;
-            float u0, u1, l0 = 0, l1 = 0;
+            // (dimension 2 is read for a moving camera alone; the table then has a time column)
+            float u0, u1, l0 = 0, l1 = 0, time = 0;
             if (S.stab_cam) {
                 idx = sample_slot(S, px, py, k);
                 const float2 cu = S.stab_cam[idx];
@@ -45,6 +48,7 @@ __global__ __launch_bounds__(kBlock) void k_generate(DScene S, PassDesc P, PassB
                     const float2 cl = S.stab_lens[idx];
                     l0 = cl.x, l1 = cl.y;
                 }
+                if (MOT) time = camera_ray_time(S, camera_motion(S)->stab_time[idx]);
             } else {
                 idx = sample_index(S, px, py, k);
                 u0 = sample_dimension(S, idx, 0, px, py), u1 = sample_dimension(S, idx, 1, px, py);
@@ -52,13 +56,14 @@ __global__ __launch_bounds__(kBlock) void k_generate(DScene S, PassDesc P, PassB
                     l0 = sample_dimension(S, idx, 3);
                     l1 = sample_dimension(S, idx, 4);
                 }
+                if (MOT) time = camera_ray_time(S, sample_dimension(S, idx, 2));
             }
             if (P.probe_mode) {
                 const uint32_t probe = (pid / uint32_t(P.kc)) / (256u * uint32_t(P.probe_tiles));
                 probe_ray(S, P.probe_cams[probe], float(px) + u0, float(py) + u1, &o, &d, &tmax);
                 B.aux[pid] = make_float4(0, 0, 0, -1.f);  // no intersection: normal 0, NO_INTERSECTION_DISTANCE
             } else
-                camera_ray(S, float(px) + u0, float(py) + u1, l0, l1, &o, &d, &tmax);
+                camera_ray<true, MOT>(S, float(px) + u0, float(py) + u1, l0, l1, &o, &d, &tmax, 0.f, time);
             if (!P.list_px && !P.probe_mode) flag_whole_film_position(B, pid, px, py, k, float(px) + u0, float(py) + u1, u0, u1);
             B.hindex[pid] = idx;
             B.L[pid] = make_float4(0, 0, 0, 0);
@@ -137,8 +142,12 @@ __global__ __launch_bounds__(kBlock) void k_mis_lit(DScene S, PassBuffers B, int
 // ---------------------------------------------------------------------------
 // launchers
 void launch_generate(const DScene &S, const PassDesc &P, const PassBuffers &B, const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_generate, dim3(grid_blocks(P.n_paths, cfg.n_cus, 8)), dim3(kBlock), 0, cfg.stream, S, P, B,
-                       cfg.count_stats ? 1 : 0);
+    if (cfg.camera_moves && !P.probe_mode)
+        hipLaunchKernelGGL(k_generate<true>, dim3(grid_blocks(P.n_paths, cfg.n_cus, 8)), dim3(kBlock), 0, cfg.stream, S, P, B,
+                           cfg.count_stats ? 1 : 0);
+    else
+        hipLaunchKernelGGL(k_generate<false>, dim3(grid_blocks(P.n_paths, cfg.n_cus, 8)), dim3(kBlock), 0, cfg.stream, S, P, B,
+                           cfg.count_stats ? 1 : 0);
 }
 void launch_miss(const DScene &S, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg) {
     const dim3 grid(grid_blocks(max_rays, cfg.n_cus, 8));

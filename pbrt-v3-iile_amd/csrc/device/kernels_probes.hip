@@ -29,9 +29,22 @@ __global__ void k_camera(DScene S, int n, const float *pfilm, const float *plens
     put3(o + 3 * i, ro);
     put3(d + 3 * i, rd);
 }
-void launch_camera(const DScene &S, int n, const float *pfilm, const float *plens, float *o, float *d,
+// the same for a moving camera (camera_motion, dscene.h) at ray time `time` (not a time sample: the shutter does not enter)
+__global__ void k_camera_at(DScene S, int n, const float *pfilm, const float *plens, float time, float *o, float *d) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    F3 ro, rd;
+    float tm;
+    camera_ray<true, true>(S, pfilm[2 * i], pfilm[2 * i + 1], plens ? plens[2 * i] : 0.f, plens ? plens[2 * i + 1] : 0.f, &ro, &rd, &tm, 0.f, time);
+    put3(o + 3 * i, ro);
+    put3(d + 3 * i, rd);
+}
+void launch_camera(const DScene &S, int n, const float *pfilm, const float *plens, float time, float *o, float *d,
                    const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_camera, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, pfilm, plens, o, d);
+    if (cfg.camera_moves)
+        hipLaunchKernelGGL(k_camera_at, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, pfilm, plens, time, o, d);
+    else
+        hipLaunchKernelGGL(k_camera, dim3((n + 255) / 256), dim3(256), 0, cfg.stream, S, n, pfilm, plens, o, d);
 }
 // BSDF in a canonical frame (ns = +z, ss = +x; the geometric normal ng, +z unless a test tilts it). sample == 0: out = {f.xyz, pdf}
 // for (wo, wi); sample == 1: out = {wi.xyz, f.xyz, pdf} for (wo, u); sample == 2: the same sample with the specular lobes allowed

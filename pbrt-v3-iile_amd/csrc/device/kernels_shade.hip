@@ -36,6 +36,7 @@ DEV F3 sample_li_plain(const DScene &S, const DLight &lt, F3 po, float u0, float
     return area_light_L(lt, ps.n, -wi);
 }
 DEV float lerp_f(float t, float a, float b) { return (1 - t) * a + t * b; }  // pbrt.h:414
+#ifndef IILE_SHADE_MOTION_TU
 // SpatialLightDistribution::ComputeDistribution (lightdistrib.cpp:228-299) in two kernels over the table of `stride` = 2 n + 2
 // floats per voxel. samples: RadicalInverse(0..4, i) for i < 128 (host table).
 // k_light_contrib: one thread per (voxel, light) — blockIdx.y is the light, so a wavefront's lanes share it and sample_li_plain's
@@ -110,6 +111,12 @@ __global__ __launch_bounds__(256) void k_sample_table(DScene S, float2 *cam, flo
     rec[0] = make_float4(r[0], r[1], r[2], r[3]);
     rec[1] = make_float4(r[4], r[5], r[6], r[7]);
 }
+// the table's time column for a moving camera (DCameraMotion::stab_time): dimension 2 of every slot
+__global__ __launch_bounds__(256) void k_sample_table_time(DScene S, float *time) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= S.stab_slots) return;
+    time[slot] = sample_dimension(S, slot_halton_index(S, slot), 2);
+}
 // test probe: the table's entries for sample k[i] of pixel (px[i], py[i]); bounce[i] >= 0: the eight dimensions of that bounce's
 // record, bounce[i] < 0: the camera part {u0, u1, l0, l1, 0, 0, 0, 0} (l0 = l1 = 0 without a lens part)
 __global__ void k_sample_table_read(DScene S, int n, const int *px, const int *py, const int *k, const int *bounce, float *out) {
@@ -128,6 +135,7 @@ __global__ void k_sample_table_read(DScene S, int n, const int *px, const int *p
     reinterpret_cast<float4 *>(out)[2 * size_t(i)] = a;
     reinterpret_cast<float4 *>(out)[2 * size_t(i) + 1] = b;
 }
+#endif  // !IILE_SHADE_MOTION_TU
 
 // shade: one bounce of PathIntegrator::Li (path.cpp:81-191) for every hit of the
 // queue that extend just resolved.
@@ -155,10 +163,16 @@ constexpr int shade_waves(bool tex, bool disney = false) { return disney ? IILE_
 #endif
 // DIS: the scene has a Disney material (DScene::disney_build): the vertex's BSDF is a DisneyBsdf (dbsdf.h), always in the textured
 //   flavour. The instrumented build includes it.
-template <bool COUNT, bool EXT, bool TEX, bool TAB = false, bool DIS = false>
+// MOT: the scene's camera moves (LaunchCfg::camera_moves) and some material reads a texture: the camera differentials rebuilt at the first
+//   vertex go through the transform at the ray's time. Three builds only — the instrumented one and the two Disney builds, which
+//   shade every material — so that no build of a scene whose camera stands still carries any of it. They are compiled in a
+//   translation unit of their own, kernels_shade_motion.hip, which includes this file with IILE_SHADE_MOTION_TU set: it takes
+//   the kernel template and its helpers from here, leaves out every other kernel and launcher, and defines launch_shade_motion.
+template <bool COUNT, bool EXT, bool TEX, bool TAB = false, bool DIS = false, bool MOT = false>
 __global__ __launch_bounds__(kBlock, shade_waves(TEX, DIS)) void k_shade(DScene S, PassDesc P, PassBuffers B, int bounce, uint32_t plane) {
     static_assert(!(TAB && COUNT), "the instrumented build keeps the digit chains");
     static_assert(!DIS || (EXT && TEX && !COUNT), "the Disney builds are textured ones");
+    static_assert(!MOT || (TEX && (DIS || COUNT)), "the moving camera's builds are the instrumented one and the Disney builds");
     constexpr bool DZ = DIS || COUNT;
     typename std::conditional<TAB, const uint16_t *, lds_u16 *>::type s_perms;
     if constexpr (TAB) {
@@ -355,7 +369,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX, DIS)) void k_shade(DScene 
                                 int px = 0, py = 0;
                                 uint32_t kk = 0;
                                 path_pixel(S, P, pid, &px, &py, &kk);
-                                float u0, u1, l0 = 0, l1 = 0;
+                                float u0, u1, l0 = 0, l1 = 0, time = 0;
                                 if (TAB) {
                                     const float2 cu = S.stab_cam[hidx];
                                     u0 = cu.x, u1 = cu.y;
@@ -363,17 +377,19 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX, DIS)) void k_shade(DScene 
                                         const float2 cl = S.stab_lens[hidx];
                                         l0 = cl.x, l1 = cl.y;
                                     }
+                                    if (MOT) time = camera_ray_time(S, camera_motion(S)->stab_time[hidx]);
                                 } else {
                                     u0 = sample_dimension(S, s_perms, hidx, 0, px, py), u1 = sample_dimension(S, s_perms, hidx, 1, px, py);
                                     if (S.lens_radius > 0) {
                                         l0 = sample_dimension(S, s_perms, hidx, 3);
                                         l1 = sample_dimension(S, s_perms, hidx, 4);
                                     }
+                                    if (MOT) time = camera_ray_time(S, sample_dimension(S, s_perms, hidx, 2));  // the time k_generate drew
                                 }
                                 const RayDiff rdiff =
                                     S.probe_mode ? probe_differentials(S, P.probe_cams[(pid / uint32_t(P.kc)) / (256u * uint32_t(P.probe_tiles))],
                                                                        float(px) + u0, float(py) + u1, ray_o, ray_d)
-                                                 : camera_differentials(S, float(px) + u0, float(py) + u1, l0, l1, ray_o, ray_d);
+                                                 : camera_differentials<MOT>(S, float(px) + u0, float(py) + u1, l0, l1, ray_o, ray_d, time);
                                 td = compute_differentials(is, rdiff, &dpdx, &dpdy);
                             }
                             if (m0.bump_tex >= 0) bump(S, m0.bump_tex, td, dpdx, dpdy, &is);  // `if (bumpMap) Bump(bumpMap, si)` comes first
@@ -544,9 +560,24 @@ __global__ __launch_bounds__(kBlock, shade_waves(TEX, DIS)) void k_shade(DScene 
 
 // ---------------------------------------------------------------------------
 // launchers
+#ifdef IILE_SHADE_MOTION_TU
+// a moving camera whose differentials are read (some material is textured, or the instrumented build runs): the Disney builds,
+// which shade every material, with the sample table or without
+void launch_shade_motion(const DScene &S, const PassDesc &P, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg) {
+    const dim3 grid(grid_blocks(max_rays, cfg.n_cus, shade_waves(true, !cfg.count_stats)));
+    const size_t perm_bytes = S.sobol ? size_t(16) : (size_t(S.n_perms) * sizeof(uint16_t) + 15) & ~size_t(15);
+    if (cfg.count_stats)
+        hipLaunchKernelGGL((k_shade<true, true, true, false, false, true>), grid, dim3(kBlock), perm_bytes, cfg.stream, S, P, B, bounce, B.queue_cap);
+    else if (S.stab_shade)
+        hipLaunchKernelGGL((k_shade<false, true, true, true, true, true>), grid, dim3(kBlock), 0, cfg.stream, S, P, B, bounce, B.queue_cap);
+    else
+        hipLaunchKernelGGL((k_shade<false, true, true, false, true, true>), grid, dim3(kBlock), perm_bytes, cfg.stream, S, P, B, bounce, B.queue_cap);
+}
+#else
 void launch_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int bounce, uint32_t max_rays, const LaunchCfg &cfg) {
     // as many blocks as are resident at the build's waves per SIMD: the static split has no tail
     const bool tex_build = cfg.count_stats || S.textured_materials || S.probe_mode;
+    if (cfg.camera_moves && tex_build && !S.probe_mode) return launch_shade_motion(S, P, B, bounce, max_rays, cfg);
     const bool dis_build = S.disney_build && !cfg.count_stats;
     const dim3 grid(grid_blocks(max_rays, cfg.n_cus, shade_waves(tex_build, dis_build)));
     const size_t perm_bytes = S.sobol ? size_t(16) : (size_t(S.n_perms) * sizeof(uint16_t) + 15) & ~size_t(15);
@@ -580,6 +611,9 @@ void launch_shade(const DScene &S, const PassDesc &P, const PassBuffers &B, int 
 void launch_sample_table(const DScene &S, float2 *cam, float2 *lens, float4 *shade, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_sample_table, dim3((S.stab_slots + 255) / 256, 1 + S.max_depth), dim3(256), 0, cfg.stream, S, cam, lens, shade);
 }
+void launch_sample_table_time(const DScene &S, float *time, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_sample_table_time, dim3((S.stab_slots + 255) / 256), dim3(256), 0, cfg.stream, S, time);
+}
 void launch_sample_table_read(const DScene &S, int n, const int *px, const int *py, const int *k, const int *bounce, float *out, const LaunchCfg &cfg) {
     hipLaunchKernelGGL(k_sample_table_read, dim3((n + 127) / 128), dim3(128), 0, cfg.stream, S, n, px, py, k, bounce, out);
 }
@@ -596,5 +630,7 @@ void launch_light_distributions(const DScene &S, const float *samples, float *ou
     }
     hipLaunchKernelGGL(k_light_cdf, dim3((n + 127) / 128), dim3(128), 0, cfg.stream, S, out);
 }
+
+#endif  // IILE_SHADE_MOTION_TU
 
 }  // namespace iile

@@ -274,6 +274,24 @@ bool finalize_scene(HostScene *s, std::string *err) {
     }
     d.camera.shutter_open = s->shutter_open;
     d.camera.shutter_close = s->shutter_close;
+    // A moving camera: AnimatedTransform(CameraToWorld[0], transformStartTime, CameraToWorld[1], transformEndTime), api.cpp:802,
+    // transform.cpp:396-411. The descriptor above is the start transform's, the same bytes a static camera there would give.
+    std::memset(&s->motion, 0, sizeof(s->motion));
+    if (s->camera_moves) {
+        iile_camera_motion &mo = s->motion;
+        mo.start_time = s->transform_start_time;
+        mo.end_time = s->transform_end_time;
+        std::memcpy(mo.camera_to_world_end, s->camera_to_world_end.m.m, sizeof(float) * 16);
+        V3 T[2];
+        Mat4 S[2];
+        bool has_rotation;
+        animated_transform(s->camera_to_world.m, s->camera_to_world_end.m, T, mo.R, S, &has_rotation);
+        for (int i = 0; i < 2; ++i) {
+            mo.T[i][0] = T[i].x, mo.T[i][1] = T[i].y, mo.T[i][2] = T[i].z;
+            std::memcpy(mo.S[i], S[i].m, sizeof(float) * 16);
+        }
+        mo.has_rotation = has_rotation ? 1 : 0;
+    }
 
     // HaltonSampler ctor, samplers/halton.cpp:65-93 (kMaxResolution = 128)
     iile_halton &h = d.halton;

@@ -69,6 +69,18 @@ class Scene {
     std::string film_filename() const { return host_ ? iile_host_scene_film_filename(host_) : std::string(); }
     // Integrator "ambientocclusion": its "nsamples" / "cossample" (CreateAOIntegrator, ao.cpp:122-124); false for any other scene
     bool ao(iile_ao_params *out) const { return host_ && integrator() == IILE_INTEGRATOR_AO && iile_host_scene_ao(host_, out) == 0; }
+    // A moving camera (`ActiveTransform` left the camera's two transforms different): its motion, else false
+    bool camera_motion(iile_camera_motion *out) const { return host_ && iile_host_scene_camera_motion(host_, out) == 0; }
+    // iile_scene_create on the current device, then the camera's motion where it has one: what every device of a frame gets
+    int CreateDeviceScene(iile_scene **gpu) const {
+        int rc = iile_scene_create(desc(), gpu);
+        iile_camera_motion motion;
+        if (rc == IILE_OK && camera_motion(&motion) && (rc = iile_scene_set_camera_motion(*gpu, &motion)) != IILE_OK) {
+            iile_scene_destroy(*gpu);
+            *gpu = nullptr;
+        }
+        return rc;
+    }
     // SamplerIntegrator::Render with the Li of the scene file's integrator: AOIntegrator's for "ambientocclusion", else PathIntegrator's
     int RenderFrame(iile_scene *gpu, const iile_render_params *prm, float *film_xyzw, iile_stats *st) const {
         iile_ao_params ao_params;
@@ -107,7 +119,7 @@ class GpuPathIntegrator : public Integrator {
         }
         if (!scene.ok()) return false;
         iile_scene *gpu = nullptr;
-        if (iile_scene_create(scene.desc(), &gpu) != IILE_OK) {
+        if (scene.CreateDeviceScene(&gpu) != IILE_OK) {
             fprintf(stderr, "Error: GPU path: %s\n", iile_last_error());
             return false;
         }
@@ -225,7 +237,7 @@ class GpuPathIntegrator : public Integrator {
         size_t n_pix = 0;
         const iile_film_desc *f = nullptr;
         bool ok = scene.ok();
-        if (ok && iile_scene_create(scene.desc(), &gpu) != IILE_OK) {
+        if (ok && scene.CreateDeviceScene(&gpu) != IILE_OK) {
             fprintf(stderr, "Error: GPU path: %s\n", iile_last_error());
             ok = false;
         }

@@ -119,6 +119,71 @@ bool xf_lookat(V3 pos, V3 look, V3 up, Xform *out) {
     return true;
 }
 
+// Quaternion(const Transform &), core/quaternion.cpp:61-92; q = {x, y, z, w}
+static void quaternion_of(const Mat4 &m, float q[4]) {
+    const float trace = m.m[0][0] + m.m[1][1] + m.m[2][2];
+    if (trace > 0.f) {
+        float s = std::sqrt(trace + 1.0f);
+        q[3] = s / 2.0f;
+        s = 0.5f / s;
+        q[0] = (m.m[2][1] - m.m[1][2]) * s;
+        q[1] = (m.m[0][2] - m.m[2][0]) * s;
+        q[2] = (m.m[1][0] - m.m[0][1]) * s;
+    } else {
+        const int nxt[3] = {1, 2, 0};
+        int i = 0;
+        if (m.m[1][1] > m.m[0][0]) i = 1;
+        if (m.m[2][2] > m.m[i][i]) i = 2;
+        const int j = nxt[i], k = nxt[j];
+        float s = std::sqrt((m.m[i][i] - (m.m[j][j] + m.m[k][k])) + 1.0f);
+        q[i] = s * 0.5f;
+        if (s != 0.f) s = 0.5f / s;
+        q[3] = (m.m[k][j] - m.m[j][k]) * s;
+        q[j] = (m.m[j][i] + m.m[i][j]) * s;
+        q[k] = (m.m[k][i] + m.m[i][k]) * s;
+    }
+}
+
+// AnimatedTransform::Decompose, core/transform.cpp:1103-1142, step for step: the translation column, then the polar
+// iteration R <- (R + (R^T)^-1) / 2 until the largest row sum of the change is at most 1e-4 (100 steps at the most), the
+// quaternion of that R, and S = R^-1 M. (Where the inverse refuses a singular matrix the identity stands in; the reference
+// reports "Singular matrix" there. No camera transform the loader makes is singular: Camera inverts it first.)
+void decompose(const Mat4 &m, V3 *T, float Rquat[4], Mat4 *S) {
+    *T = V3(m.m[0][3], m.m[1][3], m.m[2][3]);
+    Mat4 M = m;
+    for (int i = 0; i < 3; ++i) M.m[i][3] = M.m[3][i] = 0.f;
+    M.m[3][3] = 1.f;
+    float norm;
+    int count = 0;
+    Mat4 R = M;
+    do {
+        Mat4 Rnext, Rit;
+        invert(transpose(R), &Rit);
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) Rnext.m[i][j] = 0.5f * (R.m[i][j] + Rit.m[i][j]);
+        norm = 0;
+        for (int i = 0; i < 3; ++i) {
+            const float n = std::abs(R.m[i][0] - Rnext.m[i][0]) + std::abs(R.m[i][1] - Rnext.m[i][1]) + std::abs(R.m[i][2] - Rnext.m[i][2]);
+            norm = std::max(norm, n);
+        }
+        R = Rnext;
+    } while (++count < 100 && norm > .0001);
+    quaternion_of(R, Rquat);
+    Mat4 Rinv;
+    invert(R, &Rinv);
+    *S = mul(Rinv, M);
+}
+
+// AnimatedTransform's constructor, core/transform.cpp:396-411, for two different transforms
+void animated_transform(const Mat4 &start, const Mat4 &end, V3 T[2], float R[2][4], Mat4 S[2], bool *has_rotation) {
+    decompose(start, &T[0], R[0], &S[0]);
+    decompose(end, &T[1], R[1], &S[1]);
+    auto qdot = [&]() { return (R[0][0] * R[1][0] + R[0][1] * R[1][1] + R[0][2] * R[1][2]) + R[0][3] * R[1][3]; };  // quaternion.h:117-119
+    if (qdot() < 0)
+        for (int i = 0; i < 4; ++i) R[1][i] = -R[1][i];
+    *has_rotation = qdot() < 0.9995f;
+}
+
 // core/transform.cpp:303-311
 Xform xf_perspective(float fov, float n, float f) {
     Mat4 persp(1, 0, 0, 0, 0, 1, 0, 0, 0, 0, f / (f - n), -f * n / (f - n), 0, 0, 1, 0);

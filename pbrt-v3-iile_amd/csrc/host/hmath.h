@@ -181,4 +181,16 @@ Xform xf_rotate(float theta, V3 axis);
 bool xf_lookat(V3 pos, V3 look, V3 up, Xform *out);
 Xform xf_perspective(float fov, float n, float f);
 
+// AnimatedTransform::Decompose (core/transform.cpp:1103-1142): m = Translate(T) * Rotation(Rquat = {x, y, z, w}) * S
+void decompose(const Mat4 &m, V3 *T, float Rquat[4], Mat4 *S);
+// AnimatedTransform's constructor (core/transform.cpp:396-411): both decompositions, R[1] negated onto R[0]'s side
+void animated_transform(const Mat4 &start, const Mat4 &end, V3 T[2], float R[2][4], Mat4 S[2], bool *has_rotation);
+// Transform::operator!= (core/transform.h:140-146)
+inline bool differs(const Mat4 &a, const Mat4 &b) {
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j)
+            if (a.m[i][j] != b.m[i][j]) return true;
+    return false;
+}
+
 }  // namespace iile

@@ -96,6 +96,19 @@ int iile_host_scene_camera(const iile_host_scene *scene, iile_camera *out) {
     return iile_camera_kind(out);
 }
 
+int iile_host_scene_camera_motion(const iile_host_scene *scene, iile_camera_motion *out) {
+    if (!scene || !out) {
+        g_err = "iile_host_scene_camera_motion: null argument";
+        return 1;
+    }
+    if (!scene->s.camera_moves) {
+        g_err = "iile_host_scene_camera_motion: the scene's camera does not move (its start and end transforms are equal)";
+        return 2;
+    }
+    *out = scene->s.motion;
+    return 0;
+}
+
 int iile_host_scene_get_info(const iile_host_scene *scene, iile_host_scene_info *info) {
     if (!scene || !info) {
         g_err = "iile_host_scene_get_info: null argument";

@@ -41,6 +41,12 @@ struct HostScene {
 
     // camera / film / sampler / integrator options gathered before WorldBegin
     Xform camera_to_world;
+    // `ActiveTransform` / `TransformTimes`: the camera's transform at transform_end_time (camera_to_world is the one at
+    // transform_start_time). camera_moves: the two differ (AnimatedTransform::actuallyAnimated); finalize then fills `motion`
+    Xform camera_to_world_end;
+    float transform_start_time = 0.f, transform_end_time = 1.f;
+    bool camera_moves = false;
+    iile_camera_motion motion = {};
     std::string camera_name = "perspective";
     float fov = 90.f, lens_radius = 0.f, focal_distance = 1e6f;
     float shutter_open = 0.f, shutter_close = 1.f;

@@ -28,6 +28,7 @@ bool Loader::light_source(const std::string &name, const ParamSet &ps) {
     if (name != "point" && name != "spot" && name != "distant" && !infinite && !image)
         return fail("LightSource \"" + name +
                     "\" is not supported (point, spot, distant, infinite, exinfinite, projection, goniometric; area lights)");
+    warn_if_animated("LightSource");  // pbrtLightSource, api.cpp:1346: every light below is made with the start transform
     float I[3] = {1, 1, 1}, sc[3] = {1, 1, 1};
     ps.rgb((name == "distant" || infinite) ? "L" : "I", I);
     ps.rgb("scale", sc);
@@ -59,7 +60,7 @@ bool Loader::light_source(const std::string &name, const ParamSet &ps) {
 }
 
 void Loader::point_light(const V3 &from, iile_light *lt) {  // CreatePointLight, lights/point.cpp:80-88
-    const Xform l2w = xf_translate(from) * ctm_;
+    const Xform l2w = xf_translate(from) * ctm();
     lt->type = IILE_LIGHT_POINT;
     set_pos(l2w.point(V3(0, 0, 0)), lt);
 }
@@ -78,7 +79,7 @@ void Loader::spot_light(const ParamSet &ps, const V3 &from, const V3 &to, iile_l
     for (int r = 0; r < 4; ++r)
         for (int c = 0; c < 4; ++c) m.m[r][c] = rows[r][c];
     const Xform dir_to_z(m);
-    const Xform l2w = ctm_ * xf_translate(from) * inverse(dir_to_z);
+    const Xform l2w = ctm() * xf_translate(from) * inverse(dir_to_z);
     lt->type = IILE_LIGHT_SPOT;
     set_pos(l2w.point(V3(0, 0, 0)), lt);
     copy_3x3(l2w.inv, lt->w2l);                          // WorldToLight = Inverse(LightToWorld)
@@ -88,7 +89,7 @@ void Loader::spot_light(const ParamSet &ps, const V3 &from, const V3 &to, iile_l
 
 void Loader::distant_light(const V3 &from, const V3 &to, iile_light *lt) {  // CreateDistantLight, lights/distant.cpp:94-102; ctor :43-48
     lt->type = IILE_LIGHT_DISTANT;
-    set_pos(normalize(ctm_.vector(from - to)), lt);
+    set_pos(normalize(ctm().vector(from - to)), lt);
     // world_radius is set once the scene bounds are known (finalize_scene)
 }
 
@@ -105,8 +106,8 @@ bool Loader::read_light_map(const ParamSet &ps, std::vector<float> *rgb, int *w,
 bool Loader::infinite_light(const ParamSet &ps, iile_light *lt) {  // CreateInfiniteLight, lights/infinite.cpp:176-186
     lt->type = IILE_LIGHT_INFINITE;
     lt->n_samples = ps.one_int("samples", ps.one_int("nsamples", 1));  // infinite.cpp:181-182
-    copy_3x3(ctm_.m, lt->l2w);
-    copy_3x3(ctm_.inv, lt->w2l);
+    copy_3x3(ctm().m, lt->l2w);
+    copy_3x3(ctm().inv, lt->w2l);
     // InfiniteAreaLight ctor (infinite.cpp:42-84): Lmap = the environment map times L (one texel of L
     // without a map or when it cannot be read), not flipped; then the sampling distribution
     std::vector<float> rgb;
@@ -133,8 +134,8 @@ bool Loader::infinite_light(const ParamSet &ps, iile_light *lt) {  // CreateInfi
 // (lights/goniometric.cpp:86-94) and its ctor (goniometric.h:57-68): the CTM is LightToWorld
 bool Loader::image_light(const std::string &name, const ParamSet &ps, iile_light *lt) {
     lt->type = name == "projection" ? IILE_LIGHT_PROJECTION : IILE_LIGHT_GONIOMETRIC;
-    set_pos(ctm_.point(V3(0, 0, 0)), lt);
-    copy_3x3(ctm_.inv, lt->w2l);  // WorldToLight = Inverse(LightToWorld)
+    set_pos(ctm().point(V3(0, 0, 0)), lt);
+    copy_3x3(ctm().inv, lt->w2l);  // WorldToLight = Inverse(LightToWorld)
     // the map as ReadImage returns it (not times I, not flipped), under MIPMap<RGBSpectrum>(resolution, texels)'s
     // defaults; a name that cannot be read is the reference's null map (a warning, no failure)
     lt->env_tex = -1;

@@ -5,8 +5,13 @@
 namespace iile {
 
 bool Loader::make_shape(const std::string &name, const ParamSet &ps) {
+    // pbrtShape under an animated CTM (api.cpp:1406-1447) makes a TransformedPrimitive over a BVH of the shape's own: a moving
+    // instance, which this path does not have. Refused by name: the camera's motion alone is rendered.
+    if (ctms_.animated())
+        return fail(std::string("Shape \"") + name + "\"" + (gs_.has_area_light ? " (and the AreaLightSource on it)" : "") +
+                    " under an animated transform (ActiveTransform) is not supported: camera motion only, moving shapes are not rendered");
     HostPrim pr;  // what every primitive of this shape starts from
-    pr.flags = (gs_.reverse_orientation ^ ctm_.swaps_handedness()) ? IILE_PRIM_FLIP : 0;
+    pr.flags = (gs_.reverse_orientation ^ ctm().swaps_handedness()) ? IILE_PRIM_FLIP : 0;
     pr.material = current_material();
     if (pr.material < 0) return false;
     if (name == "sphere") {
@@ -36,7 +41,7 @@ void Loader::add_primitive(int light_type, HostPrim *pr) {
 }
 
 void Loader::sphere_shape(const ParamSet &ps, HostPrim *pr) {  // shapes/sphere.cpp:318-327, sphere.h:50-60
-    const Xform &o2w = ctm_;
+    const Xform &o2w = ctm();
     float radius = ps.one_float("radius", 1.f);
     float zmin = ps.one_float("zmin", -radius);
     float zmax = ps.one_float("zmax", radius);
@@ -62,7 +67,7 @@ void Loader::sphere_shape(const ParamSet &ps, HostPrim *pr) {  // shapes/sphere.
 }
 
 bool Loader::quadric_shape(const std::string &name, const ParamSet &ps, HostPrim *pr) {
-    const Xform &o2w = ctm_;
+    const Xform &o2w = ctm();
     if (scene_->quadrics.size() >= size_t(IILE_MAX_QUADRICS))
         return fail("Shape \"" + name + "\": more than " + std::to_string(IILE_MAX_QUADRICS) +
                     " disks and cylinders in one scene (the GPU renderer's limit)");
@@ -165,7 +170,7 @@ bool Loader::alpha_masks(const ParamSet &ps, int alpha_mask[2]) {
 // one primitive per triangle, each a copy of `proto` with its vertices in world space
 bool Loader::mesh_shape(const std::string &name, const ParamSet &ps, const HostPrim &proto) {
     HostScene &s = *scene_;
-    const Xform o2w = ctm_;
+    const Xform o2w = ctm();
     std::vector<int> indices;
     std::vector<V3> P, N;
     std::vector<float> uv;

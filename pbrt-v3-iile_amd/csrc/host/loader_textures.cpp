@@ -129,7 +129,7 @@ bool Loader::mapping_2d(const std::string &tex_name, const ParamSet &ps, iile_te
         t->dv = ps.one_float("vdelta", 0.f);
     } else if (type == "spherical" || type == "cylindrical") {  // Inverse(tex2world): the CTM's inverse
         t->mapping = type == "spherical" ? IILE_MAP_SPHERICAL : IILE_MAP_CYLINDRICAL;
-        if (!affine_3x4(ctm_.inv, tex_name, t->xf)) return false;
+        if (!affine_3x4(ctm().inv, tex_name, t->xf)) return false;
     } else if (type == "planar") {
         t->mapping = IILE_MAP_PLANAR;
         const V3 v1 = find_vector(ps, "v1", V3(1, 0, 0)), v2 = find_vector(ps, "v2", V3(0, 1, 0));
@@ -157,6 +157,7 @@ bool Loader::make_texture(const std::string &name, const std::string &type, cons
     ConstTexture t;
     t.is_float = type == "float";
     if (!t.is_float && type != "spectrum" && type != "color") return fail("Texture type \"" + type + "\" unknown.");
+    warn_if_animated("Texture");  // pbrtTexture, api.cpp:1249, 1267: Make*Texture gets curTransform[0]
     bool ok;
     if (cls == "constant")  // CreateConstant*Texture, textures/constant.cpp: "value" default 1
         ok = tex_value(ps, "value", t.is_float, kOne, t.v);
@@ -227,7 +228,7 @@ bool Loader::checkerboard_texture(const std::string &name, const ParamSet &ps, C
                              aa.c_str());
             pt.aamode = IILE_AA_CLOSEDFORM;
         }
-    } else if (!affine_3x4(ctm_.m, name, pt.xf))  // IdentityMapping3D(tex2world): tex2world is its WorldToTexture
+    } else if (!affine_3x4(ctm().m, name, pt.xf))  // IdentityMapping3D(tex2world): tex2world is its WorldToTexture
         return false;
     add_procedural(pt, pt.child[0] < 0 && pt.child[1] < 0, t);
     return true;

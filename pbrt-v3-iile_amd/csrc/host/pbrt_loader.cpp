@@ -129,6 +129,7 @@ bool Loader::directive(const std::string &d, TokenStream &ts) {
     for (const char *word : {"Identity", "Translate", "Scale", "Rotate", "LookAt", "Transform", "ConcatTransform", "CoordinateSystem",
                              "CoordSysTransform"})
         if (d == word) return transform_directive(d, ts);
+    if (d == "ActiveTransform" || d == "TransformTimes") return motion_directive(d, ts);
     if (d == "Texture") return texture_directive(ts);
     if (d == "MakeNamedMaterial" || d == "NamedMaterial") return named_material_directive(d, ts);
     if (d == "Include") {
@@ -142,25 +143,28 @@ bool Loader::directive(const std::string &d, TokenStream &ts) {
 bool Loader::attribute_directive(const std::string &d) {
     if (d == "AttributeBegin") {
         gs_stack_.push_back(gs_);
-        ctm_stack_.push_back(ctm_);
+        ctm_stack_.push_back({ctms_, active_bits_});
     } else if (d == "AttributeEnd") {
         if (gs_stack_.empty()) return fail("unmatched AttributeEnd");
         gs_ = gs_stack_.back();
         gs_stack_.pop_back();
-        ctm_ = ctm_stack_.back();
+        ctms_ = ctm_stack_.back().first;
+        active_bits_ = ctm_stack_.back().second;
         ctm_stack_.pop_back();
     } else if (d == "TransformBegin") {
-        ctm_stack_.push_back(ctm_);
+        ctm_stack_.push_back({ctms_, active_bits_});
     } else if (d == "TransformEnd") {
         if (ctm_stack_.empty()) return fail("unmatched TransformEnd");
-        ctm_ = ctm_stack_.back();
+        ctms_ = ctm_stack_.back().first;
+        active_bits_ = ctm_stack_.back().second;
         ctm_stack_.pop_back();
     } else if (d == "ReverseOrientation") {
         gs_.reverse_orientation = !gs_.reverse_orientation;
     } else if (d == "WorldBegin") {  // api.cpp:1160-1168
         in_world_ = true;
-        ctm_ = Xform();
-        named_cs_["world"] = ctm_;
+        ctms_ = XformPair();
+        active_bits_ = 3;
+        named_cs_["world"] = ctms_;
     } else  // WorldEnd
         in_world_ = false;
     return true;
@@ -169,21 +173,21 @@ bool Loader::attribute_directive(const std::string &d) {
 bool Loader::transform_directive(const std::string &d, TokenStream &ts) {
     float f[16];
     if (d == "Identity") {
-        ctm_ = Xform();
+        for_active_transforms([](Xform &c) { c = Xform(); });
     } else if (d == "Translate") {  // api.cpp:934-942
         if (!ts.numbers(3, f)) return fail("Translate: expected 3 numbers");
-        ctm_ = ctm_ * xf_translate(V3(f[0], f[1], f[2]));
+        for_active_transforms([&](Xform &c) { c = c * xf_translate(V3(f[0], f[1], f[2])); });
     } else if (d == "Scale") {  // api.cpp:984-991
         if (!ts.numbers(3, f)) return fail("Scale: expected 3 numbers");
-        ctm_ = ctm_ * xf_scale(f[0], f[1], f[2]);
+        for_active_transforms([&](Xform &c) { c = c * xf_scale(f[0], f[1], f[2]); });
     } else if (d == "Rotate") {  // api.cpp:973-982
         if (!ts.numbers(4, f)) return fail("Rotate: expected 4 numbers");
-        ctm_ = ctm_ * xf_rotate(f[0], V3(f[1], f[2], f[3]));
+        for_active_transforms([&](Xform &c) { c = c * xf_rotate(f[0], V3(f[1], f[2], f[3])); });
     } else if (d == "LookAt") {  // api.cpp:993-1007
         if (!ts.numbers(9, f)) return fail("LookAt: expected 9 numbers");
         Xform la;
         xf_lookat(V3(f[0], f[1], f[2]), V3(f[3], f[4], f[5]), V3(f[6], f[7], f[8]), &la);
-        ctm_ = ctm_ * la;
+        for_active_transforms([&](Xform &c) { c = c * la; });
     } else if (d == "Transform" || d == "ConcatTransform") {  // api.cpp:944-971
         Token b = ts.next();
         if (b.kind != Token::LBracket) return fail(d + ": expected [");
@@ -192,15 +196,35 @@ bool Loader::transform_directive(const std::string &d, TokenStream &ts) {
         if (b.kind != Token::RBracket) return fail(d + ": expected ]");
         Xform x(Mat4(f[0], f[4], f[8], f[12], f[1], f[5], f[9], f[13], f[2], f[6], f[10], f[14],
                      f[3], f[7], f[11], f[15]));
-        ctm_ = (d == "Transform") ? x : ctm_ * x;
+        for_active_transforms([&](Xform &c) { c = (d == "Transform") ? x : c * x; });
     } else {  // CoordinateSystem, CoordSysTransform
         Token n = ts.next();
         if (n.kind != Token::String) return fail(d + ": expected name");
         if (d == "CoordinateSystem")
-            named_cs_[n.text] = ctm_;
+            named_cs_[n.text] = ctms_;  // the whole set, whatever is active (api.cpp:1009-1013)
         else if (named_cs_.count(n.text))
-            ctm_ = named_cs_[n.text];
+            ctms_ = named_cs_[n.text];
     }
+    return true;
+}
+
+// `ActiveTransform StartTime | EndTime | All` (api.cpp:1022-1038) and the option `TransformTimes start end` (api.cpp:1040-1047)
+bool Loader::motion_directive(const std::string &d, TokenStream &ts) {
+    if (d == "ActiveTransform") {
+        Token a = ts.next();
+        if (a.kind != Token::Word || (a.text != "StartTime" && a.text != "EndTime" && a.text != "All"))
+            return fail("ActiveTransform: expected StartTime, EndTime or All, got \"" + a.text + "\"");
+        active_bits_ = a.text == "StartTime" ? 1u : (a.text == "EndTime" ? 2u : 3u);
+        return true;
+    }
+    float f[2];
+    if (!ts.numbers(2, f)) return fail("TransformTimes: expected 2 numbers");
+    if (in_world_) {  // VERIFY_OPTIONS, api.cpp:397-406
+        std::fprintf(stderr, "Error: Options cannot be set inside world block; \"TransformTimes\" not allowed.  Ignoring.\n");
+        return true;
+    }
+    scene_->transform_start_time = f[0];
+    scene_->transform_end_time = f[1];
     return true;
 }
 
@@ -239,8 +263,14 @@ bool Loader::camera(const std::string &name, const ParamSet &ps) {
     if (name != "perspective" && name != "environment")
         return fail("only the perspective and environment cameras are supported, got " + name);
     s.camera_name = name;
-    s.camera_to_world = inverse(ctm_);
-    named_cs_["camera"] = s.camera_to_world;
+    // CameraToWorld = Inverse(curTransform), both members; the camera is an AnimatedTransform of the two, which moves where they
+    // differ (api.cpp:1118-1123, AnimatedTransform::actuallyAnimated, transform.cpp:404)
+    XformPair c2w;
+    for (int i = 0; i < 2; ++i) c2w.t[i] = inverse(ctms_.t[i]);
+    s.camera_to_world = c2w.t[0];
+    s.camera_to_world_end = c2w.t[1];
+    s.camera_moves = c2w.animated();
+    named_cs_["camera"] = c2w;
     s.shutter_open = ps.one_float("shutteropen", 0.f);
     s.shutter_close = ps.one_float("shutterclose", 1.f);
     if (s.shutter_close < s.shutter_open) std::swap(s.shutter_close, s.shutter_open);

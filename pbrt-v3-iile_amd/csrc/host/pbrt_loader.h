@@ -2,6 +2,7 @@
 // pbrt_loader.cpp (the token loop, transforms, attribute stack, options block), loader_textures.cpp, loader_materials.cpp,
 // loader_lights.cpp, loader_shapes.cpp. The way in is load_pbrt_file (host_scene.h).
 #pragma once
+#include <cstdio>
 #include <map>
 
 #include "host_scene.h"
@@ -49,6 +50,12 @@ class TokenStream {
     std::string *lex_error_;
 };
 
+// TransformSet (api.cpp:128-157): the current transform at `TransformTimes`' start and at its end
+struct XformPair {
+    Xform t[2];
+    bool animated() const { return differs(t[0].m, t[1].m) || differs(t[0].inv, t[1].inv); }
+};
+
 class Loader;
 
 // One spectrum parameter of a material: GetSpectrumTexture(name, def) of its Create*Material
@@ -83,11 +90,12 @@ class Loader {
     HostScene *scene_;
     std::string *err_;
     std::string search_dir_;
-    Xform ctm_;
-    std::map<std::string, Xform> named_cs_;
+    XformPair ctms_;
+    uint32_t active_bits_ = 3;  // activeTransformBits: bit i set = transform directives act on ctms_.t[i] (`ActiveTransform`)
+    std::map<std::string, XformPair> named_cs_;
     GraphicsState gs_;
     std::vector<GraphicsState> gs_stack_;
-    std::vector<Xform> ctm_stack_;
+    std::vector<std::pair<XformPair, uint32_t>> ctm_stack_;  // pushedTransforms with pushedActiveTransformBits
     bool in_world_ = false;
     int default_material_ = -1;
     std::string lex_error_;
@@ -98,6 +106,18 @@ class Loader {
         // the tokenizer's message is the cause (parser.cpp:199-212)
         if (err_) *err_ = lex_error_.empty() ? m : lex_error_;
         return false;
+    }
+    // The start transform: what everything but the camera is made with (WARN_IF_ANIMATED_TRANSFORM, api.cpp:422-429)
+    const Xform &ctm() const { return ctms_.t[0]; }
+    // every transform directive acts on the active members only (FOR_ACTIVE_TRANSFORMS, api.cpp:417-421)
+    template <typename F>
+    void for_active_transforms(F f) {
+        for (int i = 0; i < 2; ++i)
+            if (active_bits_ & (1u << i)) f(ctms_.t[i]);
+    }
+    void warn_if_animated(const char *what) const {
+        if (ctms_.animated())
+            std::fprintf(stderr, "Warning: Animated transformations set; ignoring for \"%s\" and using the start transform only\n", what);
     }
     // ParamSet::FindOneFilename / AbsolutePath: a relative name is relative to the scene file's directory
     std::string in_search_dir(const std::string &name) const { return (!name.empty() && name[0] == '/') ? name : search_dir_ + "/" + name; }
@@ -114,6 +134,7 @@ class Loader {
     bool directive(const std::string &d, TokenStream &ts);
     bool attribute_directive(const std::string &d);
     bool transform_directive(const std::string &d, TokenStream &ts);
+    bool motion_directive(const std::string &d, TokenStream &ts);
     bool texture_directive(TokenStream &ts);
     bool named_material_directive(const std::string &d, TokenStream &ts);
     bool camera(const std::string &name, const ParamSet &ps);
