@@ -1,7 +1,8 @@
 """The IISPT render runner's gather (second half; src/integrators/iisptrenderrunner.cpp:216-596).
 
 CPU: properties of the oracle's restatement (the reference has no test for the runner and no weights for the network, so
-parity of these functions rests on the restatement plus these properties). GPU: the device kernels against the oracle,
+parity of these functions rests on the float64 truth tests/iispt_ref.py, written from the reference's sources alone, which
+test_iispt_truth.py holds the oracle to and test_gpu_iispt_truth.py the device; these properties stay beside it). GPU: the device kernels against the oracle,
 bit for bit, on seeded synthetic "predictions" (the gather needs no network weights to be tested)."""
 import numpy as np
 import pytest
