@@ -65,7 +65,6 @@ typedef struct iile_sphere {
 
 /* Disk (src/shapes/disk.h:48-70) or Cylinder (src/shapes/cylinder.h:48-71) + Shape base, with the clamps of their
  * constructors: disk phi_max = Radians(Clamp(phimax, 0, 360)); cylinder zmin / zmax ordered, phi_max likewise. */
-#define IILE_MAX_QUADRICS 1024 /* the loader refuses scenes with more; the device checks it again */
 #define IILE_QUADRIC_DISK 0
 #define IILE_QUADRIC_CYLINDER 1
 typedef struct iile_quadric {

@@ -136,13 +136,12 @@ int bvh_depth(const iile_bvh_node *nodes, int n_nodes) {
 int check_scene_desc(const iile_scene_desc &d) {
     // what the device path supports
     if (d.n_prims >= (1 << 24)) return api_fail(IILE_ERR_UNSUPPORTED, "more than 2^24 primitives");
-    if (d.n_spheres > kMaxSpheres || d.n_materials > kMaxMaterials) return api_fail(IILE_ERR_UNSUPPORTED, "too many spheres / materials");
     if (d.n_lights < 0 || (d.n_lights > 0 && !d.lights)) return api_fail(IILE_ERR_ARG, "n_lights without lights");
     // (light_power_all lies behind the members an older caller's descriptor has: not touched unless the lights need it)
     if (d.n_lights > IILE_MAX_LIGHTS && d.integrator.light_strategy == IILE_LIGHTS_POWER && !d.light_power_all)
         return api_fail(IILE_ERR_ARG, "light_power_all is null: the power strategy over more than " + std::to_string(IILE_MAX_LIGHTS) +
                                           " lights reads every light's power there");
-    if (d.n_quadrics < 0 || d.n_quadrics > kMaxQuadrics || (d.n_quadrics > 0 && !d.quadrics))
+    if (d.n_quadrics < 0 || (d.n_quadrics > 0 && !d.quadrics))
         return api_fail(IILE_ERR_UNSUPPORTED, "too many disks and cylinders");
     for (int i = 0; i < d.n_quadrics; ++i)
         if (d.quadrics[i].kind != IILE_QUADRIC_DISK && d.quadrics[i].kind != IILE_QUADRIC_CYLINDER)
@@ -286,7 +285,7 @@ uint32_t shading_class(int material_type, bool shape) {
 void set_kernel_flags(const iile_scene_desc &d, DScene &S) {
     for (int i = 0; i < d.n_prims; ++i)
         if (prim_masked(d, i)) S.has_alpha = 1;
-    S.rare_prims = (S.has_alpha || d.n_quadrics > 0) ? 1 : 0;
+    S.rare_prims = (S.has_alpha || d.n_quadrics > 0 || d.n_spheres > kFewSpheres) ? 1 : 0;
     for (int i = 0; i < d.n_materials; ++i) {
         const iile_material &m = d.materials[i];
         if (m.type == IILE_MAT_GLASS) S.has_glass = 1;
@@ -930,8 +929,7 @@ static_assert(kLightDiffuseArea == IILE_LIGHT_DIFFUSE_AREA && kLightPoint == IIL
                   kLightAreaQuadric == IILE_LIGHT_AREA_QUADRIC && kLightProjection == IILE_LIGHT_PROJECTION &&
                   kLightGoniometric == IILE_LIGHT_GONIOMETRIC,
               "light type codes");
-static_assert(kQuadricDisk == IILE_QUADRIC_DISK && kQuadricCylinder == IILE_QUADRIC_CYLINDER && kMaxQuadrics == IILE_MAX_QUADRICS,
-              "quadric kind codes");
+static_assert(kQuadricDisk == IILE_QUADRIC_DISK && kQuadricCylinder == IILE_QUADRIC_CYLINDER, "quadric kind codes");
 static_assert(kMatMatte == IILE_MAT_MATTE && kMatPlastic == IILE_MAT_PLASTIC && kMatUber == IILE_MAT_UBER &&
                   kMatMirror == IILE_MAT_MIRROR && kMatGlass == IILE_MAT_GLASS && kMatMetal == IILE_MAT_METAL &&
                   kMatSubstrate == IILE_MAT_SUBSTRATE && kMatTranslucent == IILE_MAT_TRANSLUCENT && kMatDisney == IILE_MAT_DISNEY,

@@ -108,9 +108,9 @@ struct DHaltonDim {
     double inv_base_d; // 1.0 / base, only ever used to estimate a quotient that is then exact
 };
 constexpr int kMaxHaltonDims = 128;
-constexpr int kMaxSpheres = 8;
-constexpr int kMaxQuadrics = 1024;  // = IILE_MAX_QUADRICS (checked in api_scene.hip)
-constexpr int kMaxMaterials = 64;
+// (spheres, quadrics and materials: as many as the scene has, tables in HBM. Up to kFewSpheres spheres the common builds of the
+//  traversal kernels test them, one turn of trav_leaf's loop per distinct sphere of a wavefront; more set DScene::rare_prims)
+constexpr int kFewSpheres = 8;
 // (lights: as many as the scene has. One Distribution1D over them is a record func[n] | cdf[n + 1] | funcInt of
 //  2 n + 2 floats; the spatial strategy's table of them is capped in bytes — under 2^28 floats — in api_scene.hip)
 constexpr uint32_t light_record_floats(int n_lights) { return 2u * uint32_t(n_lights) + 2u; }
@@ -194,7 +194,7 @@ struct DScene {
     int has_uber_trans;       // some uber material has a SpecularTransmission lobe (opacity < 1 or Kt): a vertex can hold two such lobes (k_direct_tree<.., 2>)
     int has_specular;         // some material has a specular lobe (mirror, glass, uber): emitted light after such a bounce
     int has_alpha;            // some mesh has an alpha mask
-    int rare_prims;           // has_alpha, or some primitive is a disk or a cylinder: the ALPHA builds of the traversal kernels run
+    int rare_prims;           // has_alpha, some primitive is a disk or a cylinder, or more than kFewSpheres spheres: the ALPHA builds of the traversal kernels run
     int boxes_nested;         // every child box lies inside its parent's (checked at upload): the four-wide
                               // step's skipping of intermediate nodes is exact only then
     // camera

@@ -497,7 +497,8 @@ DEV bool alpha_rejects(const DScene &S, int prim, uint32_t flags, float b0, floa
 // ray_d: the float4 record holding the ray direction — only the (rare) sphere
 // test needs it, so it is re-read there instead of living in registers.
 // ALPHA: the rare build — some mesh of the scene has an alpha mask (vertex-record flag bit 12 marks its triangles), or the scene
-// has disks or cylinders (DScene::rare_prims): only this build tests quadrics, so the common build stays as it was without them
+// has disks or cylinders, or more than kFewSpheres spheres (DScene::rare_prims): only this build tests quadrics and bounds the
+// turns of its shape test, so the common build stays as it was without them
 template <bool COUNT, bool ALPHA = false>
 DEV bool trav_leaf(const DScene &S, Trav &t, const StackRef &sr, TraceStats *st, const bool any_hit,
                    const float4 *ray_d) {
@@ -523,14 +524,31 @@ DEV bool trav_leaf(const DScene &S, Trav &t, const StackRef &sr, TraceStats *st,
             // quadric (disk, cylinder): the kind is decided per turn, on the wave-uniform index
             const int sphere = (S.n_spheres == 1 && !(ALPHA && S.n_quadrics > 0)) ? 0 : S.prim_shape[prim];
             bool sphere_hit = false;
-            for (bool pending = true; pending;) {
+            if (ALPHA) {
+                // the rare build takes two turns at the most, however many shapes the wavefront's lanes hold (a scene of many
+                // small spheres or columns: up to 64 of them, and as many serial turns of the loop below). The first is the
+                // loop's: the first lane's shape from SGPRs, for every lane that shares it. Whoever is left tests its own
+                // shape in one pass, the record read through vector loads as the test asks for its fields; a sphere lane, a
+                // disk lane and a cylinder lane may sit side by side. Same functions, same operations, same bits
                 const int s_now = __builtin_amdgcn_readfirstlane(sphere);
                 if (sphere == s_now) {
-                    if (ALPHA && s_now < 0)
+                    if (s_now < 0)
                         sphere_hit = quadric_test(uniform_entry(S.quadrics, ~s_now), t.rc.o(), F3{d4.x, d4.y, d4.z}, t.tmax, &th, &od, &ph);
                     else
                         sphere_hit = sphere_test(uniform_entry(S.spheres, s_now), t.rc.o(), F3{d4.x, d4.y, d4.z}, t.tmax, &th, &od, &ph);
-                    pending = false;
+                } else if (sphere < 0) {
+                    sphere_hit = quadric_test(S.quadrics[~sphere], t.rc.o(), F3{d4.x, d4.y, d4.z}, t.tmax, &th, &od, &ph);
+                } else {
+                    sphere_hit = sphere_test(S.spheres[sphere], t.rc.o(), F3{d4.x, d4.y, d4.z}, t.tmax, &th, &od, &ph);
+                }
+            } else {
+                // the common build: at most 8 spheres and no quadric (DScene::rare_prims), one turn per distinct sphere
+                for (bool pending = true; pending;) {
+                    const int s_now = __builtin_amdgcn_readfirstlane(sphere);
+                    if (sphere == s_now) {
+                        sphere_hit = sphere_test(uniform_entry(S.spheres, s_now), t.rc.o(), F3{d4.x, d4.y, d4.z}, t.tmax, &th, &od, &ph);
+                        pending = false;
+                    }
                 }
             }
             if (sphere_hit) {

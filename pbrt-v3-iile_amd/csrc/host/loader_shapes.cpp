@@ -68,9 +68,6 @@ void Loader::sphere_shape(const ParamSet &ps, HostPrim *pr) {  // shapes/sphere.
 
 bool Loader::quadric_shape(const std::string &name, const ParamSet &ps, HostPrim *pr) {
     const Xform &o2w = ctm();
-    if (scene_->quadrics.size() >= size_t(IILE_MAX_QUADRICS))
-        return fail("Shape \"" + name + "\": more than " + std::to_string(IILE_MAX_QUADRICS) +
-                    " disks and cylinders in one scene (the GPU renderer's limit)");
     iile_quadric q;
     std::memset(&q, 0, sizeof(q));
     std::memcpy(q.o2w, o2w.m.m, sizeof(q.o2w));
